@@ -14,10 +14,17 @@ Multi-GPU (one process per GPU, torchrun): independent seeds per rank, no
 data-path collective; one RCCL all_gather of each rank's episode-log slab at
 logging time; value = lanes * steps * world / max-over-ranks time ("weak").
 
-Output: ONE JSON line on rank 0 (see the harness contract), with
+A plain run does what the headline needs and no more: build the trainer, warm
+up, time --steps steps, time one evaluation event (amortised into value), write
+the last step's outputs if --dump-outputs is given, print the line.  --full
+adds every companion measurement, each a run of its own after the headline.
+
+Output: ONE JSON line on rank 0 (see the harness contract); with --full also
   roofline      the fused env-step kernel against HBM (live HIP-event timing),
   roofline_mfma the learner (MFMA) phase against the bf16 dense peak,
-  cpu_baseline  the CPU oracle port of the same loop on the host cores.
+  cpu_baseline  the CPU oracle port of the same loop on the host cores,
+and the K sweep, seeds per GPU (streams and processes), config variants and
+the fp32 companion.
 """
 import argparse
 import glob
@@ -350,6 +357,53 @@ def whole_job(elapsed, tr, lanes, steps, world, device, ms_n):
     return t_max, total_steps / t_max, [int(v) for v in slab_all[:, 5].tolist()]
 
 
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def last_step_outputs(tr):
+    """What the last step() left with its caller, as host arrays: the lanes' next
+    observations and the actions taken, the K updates' statistics rows, the
+    episode accumulator (the last step's pending rows folded in), and the
+    learner's parameters and targets after the step's updates.  Of a statistics
+    row only the slots an update computes are kept: slots 6-7 (the shadow
+    means, filled on request by last_stats(shadow=True)) hold the kernel's NaN
+    placeholder after every update, as do TD3's actor-loss and log-temperature
+    slots 10-11 (no temperature; the actor updates every second step), so a
+    NaN in what is written is the learner's."""
+    import torch
+
+    torch.cuda.synchronize()
+    tr.flush_stats()
+    cols = [c for c in range(16) if c not in ((6, 7) if tr.agent.algo == "SAC" else (6, 7, 10, 11))]
+    named = {"obs": tr.obs, "actions": tr.actions, "learn_stats": tr.stats[:max(tr.cfg.k_updates, 1)][:, cols],
+             "episode_stats": tr.ep_stats, "params": tr.agent.params, "target_params": tr.agent.target}
+    return {k: v.detach().cpu().numpy().copy() for k, v in named.items()}
+
+
+def write_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: DIR/<name>.npy per array, float32 or float64.  An array
+    over its equal share of cap_bytes is written as a fixed sample of its rows
+    (sorted indices drawn without replacement from a generator seeded by the
+    array's name, so two runs keep the same rows)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = cap_bytes // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(share // (rows.shape[1] * a.itemsize), 1)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(rows.shape[0], keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 class DryTrainer:
     """--dry-run stand-in for VecTrainer (no HIP library, no GPU): a fixed host
     sleep per vector step, longer on higher ranks, so the N-rank plumbing
@@ -379,7 +433,7 @@ def dry_run(args):
     procs_spec = args.seed_procs if args.seed_procs is not None else ("1,2,3,4" if args.config in ("c2", "c4") else "")
     procs_T = [int(v) for v in procs_spec.split(",") if v.strip()]
     seed_procs = None
-    if procs_T and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and procs_T and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         child = ["--config", args.config, "--k-updates", str(args.k_updates), "--precision", args.precision,
                  "--loss", args.loss, "--warmup", str(args.warmup), "--slice-groups", str(args.slice_groups)]
         if args.lanes:
@@ -401,7 +455,7 @@ def dry_run(args):
     cfg = CONFIGS[args.config]
     N = args.lanes or cfg["lanes"]
     ms_n = parse_multi_steps(args.multi_steps, rank, cfg["multi_steps"])
-    procs_T = [int(v) for v in (args.seed_procs or "").split(",") if v.strip()]
+    procs_T = [int(v) for v in (args.seed_procs or "").split(",") if v.strip()] if args.full else []
     sp = SeedProcs(max(procs_T), ["--dry-run", "--warmup", "1"]) if procs_T and world == 1 else None
     tr = DryTrainer(rank)
     elapsed = timed_region(tr, args.steps, args.warmup, world, lambda: None)
@@ -594,6 +648,14 @@ def main():
                     help="the N-rank launch path with a host stand-in trainer (gloo, no GPU): plumbing test only")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--seed", type=int, default=420, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every companion measurement (CPU baselines, K sweep, seeds per "
+                         "GPU as streams and as processes, config variants, the fp32 companion, the phase pass and "
+                         "the rooflines); without it only the headline is measured and the options above that "
+                         "shape those measurements have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left with its caller (observations, "
+                         "actions, update statistics, episode statistics, parameters, targets) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.cpu_worker:  # one seed of the per-core CPU baseline (never imports the GPU library)
         r = cpu_baseline(args.lanes or 65536, args.k_updates, args.cpu_seconds, 1, replay=args.replay or (1 << 20),
@@ -610,7 +672,8 @@ def main():
     # the CPU baseline runs first, before this process opens the GPU: its worker
     # processes import torch, and the box counts every process holding the device
     cpu_lines = None
-    if not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config == "c2":
+    if (args.full and not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1
+            and args.config == "c2"):
         cfg0 = CONFIGS[args.config]
         n0, rep0 = args.lanes or cfg0["lanes"], args.replay or cfg0["replay"]
         allc = min(16, os.cpu_count() or 1)  # this GPU's host-core share on the box
@@ -628,7 +691,7 @@ def main():
     procs_spec = args.seed_procs if args.seed_procs is not None else ("1,2,3,4" if args.config in ("c2", "c4") else "")
     procs_T = [int(v) for v in procs_spec.split(",") if v.strip()]
     seed_procs = None
-    if procs_T and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and procs_T and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         child = ["--config", args.config, "--k-updates", str(args.k_updates), "--precision", args.precision,
                  "--loss", args.loss, "--warmup", str(args.warmup), "--slice-groups", str(args.slice_groups)]
         if args.lanes:
@@ -691,22 +754,28 @@ def main():
         tr.profile(2)
         tr.profile_stride(max(args.event_stride, 1))
 
-    elapsed = timed_region(tr, args.steps, args.warmup, world, torch.cuda.synchronize, on_start=_prof_on)
-    # medians of the sampled launches: a mean of 10 attached-event samples moved by
-    # one slow dispatch (another tenant's work on the box, a late event) by 10 %+
-    env_s = tr.profile_samples(1)
-    env_ms = statistics.median(env_s) if env_s else 0.0
-    env_mean_ms = statistics.mean(env_s) if env_s else 0.0
-    env_samples = len(env_s)
-    tr.profile_stride(1)
-    tr.profile(1)  # the phase pass (untimed)
-    for _ in range(10):
-        tr.step()
-    ms, cnt = tr.profile_read()
-    tr.profile(0)
-    learn_ms = ms[2] / max(cnt[2], 1)
-    act_ms = ms[0] / max(cnt[0], 1)
+    # the events are --full's: a plain run records none, its headline needs none
+    elapsed = timed_region(tr, args.steps, args.warmup, world, torch.cuda.synchronize,
+                           on_start=_prof_on if args.full else None)
+    if args.dump_outputs:  # before anything after the timed region steps the trainer again
+        dumped = write_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                               last_step_outputs(tr))
     fused = tr.last_fused()
+    if args.full:
+        # medians of the sampled launches: a mean of 10 attached-event samples moved by
+        # one slow dispatch (other work on a shared GPU host, a late event) by 10 %+
+        env_s = tr.profile_samples(1)
+        env_ms = statistics.median(env_s) if env_s else 0.0
+        env_mean_ms = statistics.mean(env_s) if env_s else 0.0
+        env_samples = len(env_s)
+        tr.profile_stride(1)
+        tr.profile(1)  # the phase pass (untimed)
+        for _ in range(10):
+            tr.step()
+        ms, cnt = tr.profile_read()
+        tr.profile(0)
+        learn_ms = ms[2] / max(cnt[2], 1)
+        act_ms = ms[0] / max(cnt[0], 1)
     # evaluation (eval_multiplicative / eval_market, 100 episodes) every eval_every
     # vector steps, timed on its own and amortised into the timed region
     ev = (lambda: tr.evaluate_market(n_eval=100, test_days=250)) if cfg["env"] == "market" else \
@@ -721,6 +790,35 @@ def main():
         elapsed += eval_s * args.steps / args.eval_every
     t_max, value, ms_per_rank = whole_job(elapsed, tr, N, args.steps, world,
                                           torch.device("cpu") if shared else dev, ms_n)
+    # the headline: all a plain run prints (--full adds its measurements below)
+    out = {
+        "metric": "env steps/sec (whole node), 64k-parallel GBM+SAC at 1/2/4/8 MI355X",
+        "value": value, "unit": "env steps/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * t_max / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
+        "data": "real: stooq_snp daily closes" if cfg["env"] == "market" else "synthetic",
+        "config": {"workload": cfg["workload"], "config": args.config, "critic_loss": args.loss,
+                   "replay_per_gpu": replay, "multi_steps": ms_n, "multi_steps_per_rank": ms_per_rank,
+                   "eval_ms_per_event": 1e3 * eval_s, "eval_every_vector_steps": args.eval_every,
+                   "lanes_per_gpu": N, "global_lanes": N * world, "k_updates_per_vector_step": K,
+                   "mini_batch": tr.batch, "topk": tr.topk, "utd_updates_per_env_step": K / N,
+                   "parallelism": f"independent seeds x{world} (no data-path collective)"
+                                  + (f"; REHEARSAL: {world} ranks sharing {ndev} GPU(s) over gloo" if shared else ""),
+                   "fused_act_env": fused},
+        "updates_per_s": K * args.steps * world / t_max,
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
+    if force_dist and world == 1:
+        out["process_group"] = f"{dist.get_backend()} at world 1 (RLMD_BENCH_FORCE_DIST)"
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if _dist_on():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # after the headline region (rank-local, no collective): K sweep at the same
     # lanes, and the fp32 companion (the reference's arithmetic) at the headline K
@@ -879,22 +977,8 @@ def main():
     mfma_tf = flops / (learn_ms * 1e-3) / 1e12 if learn_ms > 0 else None
 
     if rank == 0:
-        out = {
-            "metric": "env steps/sec (whole node), 64k-parallel GBM+SAC at 1/2/4/8 MI355X",
-            "value": value, "unit": "env steps/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * t_max / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
-            "data": "real: stooq_snp daily closes" if cfg["env"] == "market" else "synthetic",
-            "config": {"workload": cfg["workload"], "config": args.config, "critic_loss": args.loss,
-                       "replay_per_gpu": replay, "multi_steps": ms_n, "multi_steps_per_rank": ms_per_rank,
-                       "eval_ms_per_event": 1e3 * eval_s, "eval_every_vector_steps": args.eval_every,
-                       "lanes_per_gpu": N, "global_lanes": N * world, "k_updates_per_vector_step": K,
-                       "mini_batch": tr.batch, "topk": tr.topk, "utd_updates_per_env_step": K / N,
-                       "parallelism": f"independent seeds x{world} (no data-path collective)"
-                                      + (f"; REHEARSAL: {world} ranks sharing {ndev} GPU(s) over gloo" if shared else ""),
-                       "fused_act_env": fused,
-                       "phase_ms_per_step": {"act": act_ms, "env_kernel": env_ms, "learn_k": learn_ms}},
-            "updates_per_s": K * args.steps * world / t_max,
+        out["config"]["phase_ms_per_step"] = {"act": act_ms, "env_kernel": env_ms, "learn_k": learn_ms}
+        out.update({
             "seeds_per_gpu": {"note": "T independent seeds of this workload on one GPU (SeedGroup: own lanes, "
                                       "replay and learner per seed, one HIP stream each), per-GPU totals; eval not "
                                       "amortised", "streams": stream_modes[0], **per_mode[stream_modes[0]],
@@ -916,15 +1000,13 @@ def main():
                               "achieved": mfma_tf, "peak": BF16_PEAK_TFLOPS if args.precision == "bf16" else 157.3,
                               "unit": "TFLOP/s", "frac": (mfma_tf or 0) / (BF16_PEAK_TFLOPS if args.precision == "bf16" else 157.3),
                               "algorithmic_flops_per_step": flops, "avg_phase_ms": learn_ms},
-        }
+        })
         if cpu_lines is not None:
             # all host cores of this GPU's share (16 on the box), one seed each; and one core
             out["cpu_baseline"], out["cpu_baseline_1core"] = cpu_lines[:2]
             out["cpu_baseline_utd1"] = {"all_cores": cpu_lines[2], "1core": cpu_lines[3]}
         else:
             out["cpu_baseline"] = None
-        if force_dist and world == 1:
-            out["process_group"] = f"{dist.get_backend()} at world 1 (RLMD_BENCH_FORCE_DIST)"
         print(json.dumps(out), flush=True)
     if _dist_on():
         dist.barrier()

@@ -60,7 +60,7 @@ def test_seed_processes_protocol():
     and warmed on "run", started together on "go"; the group's rate is T x
     lanes x n_t over the span from the first start to the last end."""
     lanes = 64
-    out = _run("--steps", "3", "--warmup", "1", "--lanes", str(lanes), "--seed-procs", "1,2,3")
+    out = _run("--full", "--steps", "3", "--warmup", "1", "--lanes", str(lanes), "--seed-procs", "1,2,3")
     sp = out["seeds_per_gpu_processes"]
     assert sorted(sp) == ["1", "2", "3"]
     for T, r in sp.items():
@@ -70,3 +70,39 @@ def test_seed_processes_protocol():
         # end (self-calibrated, so a loaded host that slows every step still passes)
         serial = sum(ms * 5 / 1e3 for ms in r["per_seed_ms_per_step"])
         assert r["span_s"] < 0.9 * serial or int(T) == 1
+
+
+def test_plain_run_starts_no_seed_processes():
+    """Without --full the seed processes are not part of the run, whatever
+    --seed-procs says: a plain run measures the headline only."""
+    out = _run("--steps", "3", "--warmup", "1", "--lanes", "64", "--seed-procs", "1,2")
+    assert out["seeds_per_gpu_processes"] == {}
+    assert out["steps"] == 3 and out["ms_per_step"] == pytest.approx(1e3 * out["t_max_s"] / 3, rel=1e-12)
+
+
+def test_write_outputs_dtypes_and_fixed_sample(tmp_path):
+    """--dump-outputs' writer: float32 / float64 .npy files; an array over its
+    share of the cap is a row sample that is the same from call to call."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(0)
+    arrays = {"obs": rng.standard_normal((1000, 5)).astype(np.float32), "stats": rng.standard_normal(4),
+              "flags": np.arange(7, dtype=np.int32), "flat": rng.standard_normal(3000).astype(np.float32)}
+    cap = 4 * 4096  # a share of 4096 B: obs (20,000 B) and flat (12,000 B) are over it
+    shapes = bench.write_outputs(str(tmp_path / "a"), arrays, cap_bytes=cap)
+    bench.write_outputs(str(tmp_path / "b"), arrays, cap_bytes=cap)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert {n: list(g.shape) for n, g in got.items()} == shapes
+    assert got["obs"].dtype == np.float32 and got["stats"].dtype == np.float64
+    assert got["flags"].dtype == np.float32 and np.array_equal(got["flags"], np.arange(7))
+    assert np.array_equal(got["stats"], arrays["stats"])
+    assert got["obs"].shape == (4096 // 20, 5) and got["flat"].shape == (1024,)
+    assert sum(g.nbytes for g in got.values()) <= cap
+    # the sample is whole rows of the array, in order, and identical in the second call
+    keys = {tuple(r) for r in arrays["obs"].tolist()}
+    assert all(tuple(r) in keys for r in got["obs"].tolist())
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

@@ -9,6 +9,8 @@ timeout -k 10 700 python -u -m pytest -x -q --timeout 300 --timeout-method threa
   tests/test_target_pair_gpu.py tests/test_seeds_gpu.py tests/test_fused_env_gpu.py tests/test_train_gpu.py \
   tests/test_smoke_matrix_gpu.py > gpurun_out/r06_exp3_tests.log 2>&1 || { tail -30 gpurun_out/r06_exp3_tests.log; exit 1; }
 tail -2 gpurun_out/r06_exp3_tests.log
-timeout -k 10 480 python -u bench.py > gpurun_out/r06b_bench.log 2>&1 || { tail -20 gpurun_out/r06b_bench.log; exit 1; }
+LINES=${RLMD_LINES_DIR:-bench_lines}
+mkdir -p "$LINES"
+timeout -k 10 480 python -u bench.py --full > "$LINES/r06b_bench.log" 2>&1 || { tail -20 "$LINES/r06b_bench.log"; exit 1; }
 echo bench done
 timeout -k 10 600 bash tools/gpu_seeds_ab.sh r06aw4 "base:-" "aw4:RLMD_LIB_PATH=tools/_abh/librlmd_amd_aw4.so"

@@ -11,7 +11,7 @@ timeout -k 10 700 bash tools/gpu_trace_ab.sh park "c2:- c2:RLMD_LIB_PATH=tools/_
   || { tail -20 gpurun_out/r06_park_ab.log; exit 1; }
 grep -E "==|act_env|fused_act|fwd_rows" gpurun_out/tab_park/summary.txt
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-BENCH="bench.py --no-cpu-baseline --no-companion --k-sweep= --seeds-per-gpu= --seed-procs= --steps 25 --warmup 5"
+BENCH="bench.py --full --no-cpu-baseline --no-companion --k-sweep= --seeds-per-gpu= --seed-procs= --steps 25 --warmup 5"
 OUT=gpurun_out/prof_park
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "act_env_kernel|fused_act_kernel|env_train_kernel" -f csv -d $OUT/fetch -o fetch -- python3 $BENCH > $OUT/fetch.log 2>&1 || exit 1

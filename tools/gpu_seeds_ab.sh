@@ -12,7 +12,7 @@ for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
   [ "$envs" = "-" ] && envs=""
   echo "== $name ($envs)"
-  env $envs timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-companion \
+  env $envs timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-companion \
       --k-sweep '' --seed-procs '' --seeds-per-gpu "${SEEDS:-2,3,4}" > "$out/$name.json" 2> "$out/$name.err" || { echo "FAIL $name"; exit 1; }
   python - "$out/$name.json" <<'EOF'
 import json, sys

@@ -105,7 +105,7 @@ def main(tag, config="c2"):
     shutil.copy(stats, os.path.join(dst, f"{tag}_kernel_stats.csv"))
     rows = list(csv.DictReader(open(stats)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
-    lines = [f"rocprofv3 --kernel-trace --stats: python bench.py --no-cpu-baseline --no-companion --k-sweep= "
+    lines = [f"rocprofv3 --kernel-trace --stats: python bench.py --full --no-cpu-baseline --no-companion --k-sweep= "
              f"--seeds-per-gpu= --seed-procs= --steps 25 --warmup 5 "
              f"(C2, 65,536 GBM lanes, SAC 256/256 bf16, K=8)", "",
              f"{'calls':>6} {'avg_us':>9} {'total_ms':>9} {'pct':>6}  kernel"]
@@ -171,7 +171,7 @@ def config_summaries(tag):
             continue
         rows = list(csv.DictReader(open(stats)))
         tot = sum(float(r["TotalDurationNs"]) for r in rows)
-        lines = [f"rocprofv3 --kernel-trace --stats: python bench.py --config {cfg} --no-cpu-baseline --no-companion "
+        lines = [f"rocprofv3 --kernel-trace --stats: python bench.py --full --config {cfg} --no-cpu-baseline --no-companion "
                  f"--k-sweep= --seeds-per-gpu= --seed-procs= --variants= --steps 25 --warmup 5 ({name})", "",
                  f"{'calls':>6} {'avg_us':>9} {'total_ms':>9} {'pct':>6}  kernel"]
         per_kernel = {}
