@@ -442,6 +442,15 @@ int rlmd_profile_stride(rlmd_agent_t ag, int32_t stride);
  * f32 summation order, so runs compared bit for bit must use the same budget. */
 int rlmd_agent_set_cu_budget(rlmd_agent_t ag, int32_t n_cu);
 
+/* Debug query of the hoisted replay sample (RLMD_SAMPLE_HOIST, default on): the
+ * training step's last learner launch draws the next step's index sets, and a
+ * step whose (ring population, batch, K, seed, counter) match what was drawn
+ * gathers by index inside its first forward launch instead of launching the
+ * sampler.  out2[0] = multi-update learn calls that took the hoisted path,
+ * out2[1] = calls that launched the sampler (first call, K changed, small ring,
+ * rlmd_agent_learn outside the training step, parameters written by the host). */
+int rlmd_agent_hoist_counts(rlmd_agent_t ag, int64_t* out2);
+
 /* ------------------------------------------------------------- test hooks */
 /* Copy ring rows (start + i) % capacity, i < n, into caller buffers (nullable). */
 int rlmd_replay_read(rlmd_replay_t rb, int64_t start, int64_t n, float* s_dev, float* a_dev,

@@ -119,6 +119,7 @@ SIGNATURES = {
     "rlmd_profile_stride": (C.c_int, [P, I32]),
     "rlmd_profile_samples": (C.c_int, [P, I32, P, C.c_int64, P]),
     "rlmd_agent_set_cu_budget": (C.c_int, [P, I32]),
+    "rlmd_agent_hoist_counts": (C.c_int, [P, P]),
     "rlmd_gemm": (C.c_int, [I32, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, I32, P, I32, P, P]),
 }
 
@@ -139,7 +140,12 @@ def load(path=LIB_PATH):
             "(the HIP extension is required; there is no CPU fallback)")
     lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # an A/B library (RLMD_LIB_PATH) built from an earlier commit may lack a newer query
+            if path == LIB_PATH:
+                raise RlmdError(f"{path} does not export {name}: rebuild it")
+            continue
         fn.restype = res
         fn.argtypes = args
     return lib

@@ -229,6 +229,14 @@ class DeviceAgent:
         self._seen = self._versions()
         check(_abi.lib().rlmd_agent_params_written(self.h))
 
+    def hoist_counts(self):
+        """(hoisted, fallen back): learn calls whose replay sample was drawn ahead and
+        gathered inside the first forward launch, against calls that launched the
+        sampler (rlmd_agent_hoist_counts; RLMD_SAMPLE_HOIST=0 turns the hoist off)."""
+        out = (C.c_int64 * 2)()
+        check(_abi.lib().rlmd_agent_hoist_counts(self.h, out))
+        return int(out[0]), int(out[1])
+
     def scalars(self):
         out = (C.c_double * 5)()
         check(_abi.lib().rlmd_agent_scalars(self.h, out))

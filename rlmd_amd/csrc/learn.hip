@@ -335,6 +335,20 @@ struct rlmd_agent_s {
   uint8_t* kb_done = nullptr;
   int64_t* kb_idx = nullptr;
   int32_t* kb_eff = nullptr;
+  // the sample launch hoisted off the training step's chain (agent_learn_k,
+  // RLMD_SAMPLE_HOIST=0: off): the call's last launch draws the NEXT call's K index
+  // sets into kb_idx_pre under the key below; a call whose own key equals it
+  // gathers by index inside update 0's fwd_rows instead of launching the sampler
+  bool hoist_on = true;
+  int64_t* kb_idx_pre = nullptr;
+  struct {
+    bool valid = false;
+    const void* rb = nullptr;
+    int64_t M = 0;
+    int B = 0, K = 0;
+    uint64_t seed = 0, ctr = 0;
+  } pre;
+  int64_t n_hoisted = 0, n_fallback = 0;  // calls of agent_learn_k by path (rlmd_agent_hoist_counts)
   size_t wcopy_bytes = 0;  // per copy
   float *act_h1 = nullptr, *act_h2 = nullptr;
   int64_t act_cap = 0;
@@ -576,8 +590,26 @@ struct PairCtl {
   int split;  // the pairing update's fwd column split: its target halves are this update's
 };
 
+// The hoisted sample of one agent_learn_k call as learn_body sees it.  Update 0
+// of a call with prepared index sets (gather): fwd_rows stages by index and
+// gathers the K mini-batches in extra workgroups while its grid fits the chip
+// (gathered = true), else the sample launch runs first (the fallback's
+// arguments below).  The call's last update (draw.n > 0): the next call's draw
+// rides on the update's last launch when that is a fused one and its grid fits
+// (drew = true).
+struct HoistCtl {
+  bool gather = false, gathered = false;
+  HoistGatherArgs hg{};
+  ReplayView v{};
+  int64_t M = 0;
+  int K = 0;
+  uint64_t seed = 0, ctr = 0;
+  SampleDrawArgs draw{};
+  bool drew = false;
+};
+
 int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const float* eps_b, float* stats,
-               hipStream_t st, PairCtl* pc = nullptr) {
+               hipStream_t st, PairCtl* pc = nullptr, HoistCtl* hc = nullptr) {
   const rlmd_agent_cfg& c = ag->cfg;
   Scratch& S_ = ag->sc;
   const int B = c.batch, S = c.state_dim, A = c.action_dim, X = S + A, H1 = c.h1, H2 = c.h2;
@@ -607,8 +639,8 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
   // + their U1 bases): two workgroups per (rows, job) when the grid still fits
   // the chip in one round; the halves' partial sums meet in the critic step
   int fsplit = 1;
+  const int ny = (actor_step ? 5 : 4) - (ready ? 2 : 0) + (pair ? 2 : 0);
   {
-    const int ny = (actor_step ? 5 : 4) - (ready ? 2 : 0) + (pair ? 2 : 0);
     if (ag->fused_update && ag->fsplit_max > 1 && d.H2p % 64 == 0 && 2 * ((B + 15) / 16) * ny <= ag->n_cu)
       fsplit = 2;
     // targets computed by the previous update's forward carry its split (the
@@ -616,6 +648,15 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
     if (ready) fsplit = pc->split;
     if (pc) pc->split = fsplit;
   }
+  // the hoisted gather's workgroups only while the launch still fits the chip in
+  // one round (the column split's rule); else today's launch, then plain staging
+  if (hc && hc->gather) {
+    hc->gathered = ((B + 15) / 16) * (ny + fwd_rows_gather_y(B, hc->K)) * fsplit <= ag->n_cu;
+    if (!hc->gathered)
+      RLMD_TRY(replay_sample_launch(hc->v, hc->M, B, hc->K, hc->seed, hc->ctr, hc->hg.o_idx, hc->hg.o_s, hc->hg.o_a,
+                                    hc->hg.o_r, hc->hg.o_s2, hc->hg.o_done, hc->hg.o_xsa, nullptr, st));
+  }
+  const bool want_draw = hc && hc->draw.n > 0;
 
   // ---- forward rows: target path (algo_sac.py:300-367 / algo_td3.py:302-361),
   //      critics on (s, a) (algo_sac.py:413-417), policy on s for the actor step
@@ -679,6 +720,7 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       f.qtn[1] = S_.tpartn[1];
       f.ctrn = (uint32_t)(cntr + 1);
     }
+    if (hc && hc->gathered) f.hg = hc->hg;
     RLMD_TRY(fwd_rows_launch(f, st, fsplit));
   }
   // ---- critic loss (algo_sac.py:413-465)
@@ -770,6 +812,12 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
     if (ag->fused_actor && actor_step && loss_stats.B > 0) cu.rank_out = S_.rank1;
     // no actor step: the statistics run as two workgroups of the critic step's launch
     if (loss_stats.B > 0 && !actor_step) cu.cstats = loss_stats;
+    // the call's last launch (no actor step follows): + the next call's draw
+    if (want_draw && !actor_step &&
+        2 * (cu.n_w2 + cu.n_w1 + cu.ti) + (cu.cstats.B > 0 ? 2 : 0) + hc->draw.n <= ag->n_cu) {
+      cu.draw = hc->draw;
+      hc->drew = true;
+    }
     RLMD_TRY(critic_update_launch(cu, st));
   } else {
     CBwdArgs cb{};
@@ -903,6 +951,11 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       au.n_w2 = au.ti * au.tj;
       au.n_w1 = actor_update_n_w1(d);
       au.qsplit = qsplit;
+      // the call's last launch: + the next call's draw
+      if (want_draw && au.n_w2 + au.n_w1 + au.ti + (au.cstats.B > 0 ? 2 : 0) + hc->draw.n <= ag->n_cu) {
+        au.draw = hc->draw;
+        hc->drew = true;
+      }
       RLMD_TRY(actor_update_launch(au, st));
       return 0;
     }
@@ -992,8 +1045,10 @@ float* stats_slot(rlmd_agent_s* ag, float* stats, int i) {
   return stats ? stats + 16 * (int64_t)i : ag->sc.stats;
 }
 
+// next_insert: rows the ring gains before the next call (the training step's
+// lane count; -1: unknown, nothing is drawn ahead).
 int agent_learn_k(rlmd_agent_s* ag, rlmd_replay_t rb, int k, float* stats, hipStream_t st,
-                  bool copies_current = false) {
+                  bool copies_current = false, int64_t next_insert = -1) {
   const rlmd_agent_cfg& c = ag->cfg;
   const ReplayView v = replay_view(rb);
   const int64_t mem = replay_mem_idx(rb);
@@ -1003,9 +1058,11 @@ int agent_learn_k(rlmd_agent_s* ag, rlmd_replay_t rb, int k, float* stats, hipSt
   const int B = c.batch, S = c.state_dim, A = c.action_dim;
   if (k > ag->kcap) {  // K mini-batches of scratch, grown on demand
     for (void* p : {(void*)ag->kb_s, (void*)ag->kb_a, (void*)ag->kb_r, (void*)ag->kb_s2, (void*)ag->kb_xsa,
-                    (void*)ag->kb_done, (void*)ag->kb_idx, (void*)ag->kb_eff})
+                    (void*)ag->kb_done, (void*)ag->kb_idx, (void*)ag->kb_eff, (void*)ag->kb_idx_pre})
       if (p) RLMD_HIP(hipFree(p));
+    ag->pre.valid = false;
     const size_t KB = (size_t)k * B;
+    RLMD_HIP(hipMalloc(&ag->kb_idx_pre, sizeof(int64_t) * KB));
     RLMD_HIP(hipMalloc(&ag->kb_s, sizeof(float) * KB * S));
     RLMD_HIP(hipMalloc(&ag->kb_a, sizeof(float) * KB * A));
     RLMD_HIP(hipMalloc(&ag->kb_r, sizeof(float) * KB));
@@ -1020,17 +1077,56 @@ int agent_learn_k(rlmd_agent_s* ag, rlmd_replay_t rb, int k, float* stats, hipSt
   // all K mini-batches at once: the ring does not change during the K updates;
   // batch i draws with counter learn_step_cntr + i (as K single draws would)
   const bool ms = v.n_steps > 1;
-  RLMD_TRY(replay_sample_launch(v, M, B, k, c.seed ^ 0x5eed5eed5eedull, (uint64_t)ag->host_cntr, ag->kb_idx,
-                                ag->kb_s, ag->kb_a, ag->kb_r, ag->kb_s2, ag->kb_done, ag->kb_xsa,
-                                ms ? ag->kb_eff : nullptr, st));
+  const uint64_t sseed = c.seed ^ 0x5eed5eed5eedull, ctr0 = (uint64_t)ag->host_cntr;
+  // Hoisted path: single-step rings on the fused bf16 update (the row kernels'
+  // register staging takes rows up to 8 wide, the fused update's own limit).
+  // The prepared sets serve this call only if drawn for exactly its key.
+  const bool can = ag->hoist_on && ag->fused_update && c.precision == RLMD_BF16 && !ms && S + A <= 8;
+  const bool use = can && ag->pre.valid && ag->pre.rb == (const void*)rb && ag->pre.M == M && ag->pre.B == B &&
+                   ag->pre.K == k && ag->pre.seed == sseed && ag->pre.ctr == ctr0 && M > kSortPopulation;
+  ag->pre.valid = false;
+  HoistCtl hc{};
+  hc.K = k;
+  if (use) {
+    hc.gather = true;
+    hc.hg = HoistGatherArgs{ag->kb_idx_pre, v,        ag->kb_idx, ag->kb_s, ag->kb_a,
+                            ag->kb_r,       ag->kb_s2, ag->kb_xsa, ag->kb_done, k};
+    hc.v = v;
+    hc.M = M;
+    hc.seed = sseed;
+    hc.ctr = ctr0;
+  } else {
+    RLMD_TRY(replay_sample_launch(v, M, B, k, sseed, ctr0, ag->kb_idx, ag->kb_s, ag->kb_a, ag->kb_r, ag->kb_s2,
+                                  ag->kb_done, ag->kb_xsa, ms ? ag->kb_eff : nullptr, st));
+  }
+  // the next call's ring population, when the caller knows what it inserts
+  int64_t M_next = -1;
+  if (can && next_insert >= 0) {
+    M_next = mem + next_insert < v.capacity ? mem + next_insert : v.capacity;
+    if (M_next <= kSortPopulation || M_next < B) M_next = -1;
+  }
   PairCtl pc{nullptr, false, false, 1};
   for (int i = 0; i < k; ++i) {
     const size_t o = (size_t)i * B;
     const Batch mb{ag->kb_s + o * S, ag->kb_r + o, ag->kb_s2 + o * S, ag->kb_xsa + o * (S + A), ag->kb_done + o,
                    ms ? ag->kb_eff + o : nullptr};
     pc.s2n = i + 1 < k ? ag->kb_s2 + (o + B) * S : nullptr;
-    RLMD_TRY(learn_body(ag, mb, nullptr, nullptr, stats_slot(ag, stats, i), st, &pc));
+    hc.gather = use && i == 0;
+    if (i == k - 1 && M_next > 0) hc.draw = SampleDrawArgs{M_next, sseed, ctr0 + (uint64_t)k, ag->kb_idx_pre, B, k};
+    RLMD_TRY(learn_body(ag, mb, nullptr, nullptr, stats_slot(ag, stats, i), st, &pc, &hc));
+    if (i == 0) (use && hc.gathered ? ag->n_hoisted : ag->n_fallback)++;
+    // update 0 gathered by index: the later updates read the slabs it filled
+    if (i == 0) hc.gathered = false;
     pc.ready = pc.paired;
+  }
+  if (hc.drew) {
+    ag->pre.valid = true;
+    ag->pre.rb = (const void*)rb;
+    ag->pre.M = M_next;
+    ag->pre.B = B;
+    ag->pre.K = k;
+    ag->pre.seed = sseed;
+    ag->pre.ctr = ctr0 + (uint64_t)k;
   }
   return 0;
 }
@@ -1176,6 +1272,8 @@ int rlmd_agent_create(const rlmd_agent_cfg* cfg, float* params, float* target, f
     }
     const char* tp = getenv("RLMD_TARGET_PAIR");  // default on; RLMD_TARGET_PAIR=0 turns it off
     ag->target_pair = !(tp && atoi(tp) == 0);
+    const char* sh = getenv("RLMD_SAMPLE_HOIST");  // default on; RLMD_SAMPLE_HOIST=0: the sample launch every call
+    ag->hoist_on = !(sh && atoi(sh) == 0);
     const char* nf = getenv("RLMD_NO_FUSED_UPDATE");
     ag->fused_update = B <= 512 && X <= 8 && !(nf && atoi(nf) != 0);
     const char* na = getenv("RLMD_NO_FUSED_ACTOR");
@@ -1263,7 +1361,7 @@ int rlmd_agent_destroy(rlmd_agent_t ag) {
   if (ag->act_h1) (void)hipFree(ag->act_h1);
   if (ag->act_h2) (void)hipFree(ag->act_h2);
   for (void* p : {(void*)ag->kb_s, (void*)ag->kb_a, (void*)ag->kb_r, (void*)ag->kb_s2, (void*)ag->kb_xsa,
-                  (void*)ag->kb_done, (void*)ag->kb_idx, (void*)ag->kb_eff})
+                  (void*)ag->kb_done, (void*)ag->kb_idx, (void*)ag->kb_eff, (void*)ag->kb_idx_pre})
     if (p) (void)hipFree(p);
   delete ag;
   return 0;
@@ -1321,7 +1419,15 @@ int rlmd_agent_act(rlmd_agent_t ag, const float* obs, int64_t n, float* actions,
 
 int rlmd_agent_learn(rlmd_agent_t ag, rlmd_replay_t rb, int32_t k, float* stats, void* stream) {
   RLMD_CHECK(ag && rb, "null argument");
+  ag->pre.valid = false;  // outside the training step: the sample launch (nothing was drawn for this call)
   return rlmd::agent_learn_k(ag, rb, k, stats, (hipStream_t)stream);
+}
+
+int rlmd_agent_hoist_counts(rlmd_agent_t ag, int64_t* out2) {
+  RLMD_CHECK(ag && out2, "null argument");
+  out2[0] = ag->n_hoisted;
+  out2[1] = ag->n_fallback;
+  return 0;
 }
 
 int rlmd_agent_learn_batch(rlmd_agent_t ag, const float* s, const float* a, const float* r,
@@ -1356,6 +1462,7 @@ int rlmd_debug_ts(unsigned long long* out) {
 int rlmd_agent_params_written(rlmd_agent_t ag) {
   RLMD_CHECK(ag, "null agent");
   ag->copies_dirty = true;
+  ag->pre.valid = false;  // the host stepped in: the next call samples with its own launch
   return 0;
 }
 
@@ -1513,7 +1620,7 @@ int rlmd_train_step(rlmd_env_t env, rlmd_replay_t rb, rlmd_agent_t ag, const rlm
   rlmd::replay_advance(rb, N);
   if (ag && cfg->k_updates > 0 && rlmd::replay_mem_idx(rb) > ag->cfg.batch) {
     RLMD_TRY(ag->prof.record(2, 0, st));
-    RLMD_TRY(rlmd::agent_learn_k(ag, rb, cfg->k_updates, stats, st, !random));
+    RLMD_TRY(rlmd::agent_learn_k(ag, rb, cfg->k_updates, stats, st, !random, N));
     RLMD_TRY(ag->prof.record(2, 1, st));
   }
   return 0;

@@ -7,6 +7,7 @@
 
 #include "rlmd_common.h"
 #include "rlmd_internal.h"
+#include "rlmd_replay_dev.h"
 
 namespace rlmd {
 
@@ -180,6 +181,11 @@ struct FwdRowsArgs {
   float* qtn[2];
   uint32_t ctrn;
   int32_t y0, npair;
+  // update 0 of a call whose index sets were drawn ahead (learn.hip agent_learn_k;
+  // hg.idx set, the GATHER instantiation): the row workgroups stage their rows
+  // from the ring by index — s2 / s2n / xsa / s above are then not read — and
+  // extra workgroups past the jobs gather the K mini-batches into the slabs
+  HoistGatherArgs hg;
 };
 
 // Critics evaluated on (s, a_new) after their update: y = g.
@@ -293,6 +299,7 @@ struct ABwdArgs {
 
 size_t rows_lds_bytes(const RowDims& d);
 int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split = 1);  // split: critic column halves (gridDim.z)
+int fwd_rows_gather_y(int B, int nk);  // grid rows of a.hg's gather role (nk mini-batches) past the jobs
 int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split = 1);  // split: gridDim.z column halves
 int cbwd_rows_launch(const CBwdArgs& a, hipStream_t st);
 int abwd_rows_launch(const ABwdArgs& a, hipStream_t st);

@@ -28,6 +28,7 @@
 #include <stddef.h>
 #include "rlmd_common.h"
 #include "rlmd_internal.h"
+#include "rlmd_replay_dev.h"
 
 struct rlmd_replay_s {
   rlmd::ReplayView v;
@@ -98,70 +99,10 @@ __device__ void gather_row(const rlmd::ReplayView& rb, int64_t row, int i, float
   if (done) done[i] = rb.done[row];
   if (eff) eff[i] = e;
 }
-// Single-step rows (the training loop's case): every load of the row issued
-// before its first store. In gather_row's element loops each store is counted
-// in vmcnt and the outputs may alias the ring as far as the compiler knows, so
-// every element waited on its own scattered-row round trip (S + S + A + 2 of
-// them per row). Clamped indices keep the loads branch-free; the stores are
-// write-through (the next kernel reads them).
-__device__ __forceinline__ void gather_row1(const rlmd::ReplayView& rb, int64_t row, int i, float* s, float* a,
-                                            float* r, float* s2, uint8_t* done, float* xsa, int32_t* eff) {
-  constexpr int C = 8;
-  const int S = rb.S, A = rb.A, X = S + A;
-  const float* st = rb.state + row * S;
-  const float* ns = rb.next_state + row * S;
-  const float* ac = rb.action + row * A;
-  float sv[C], nv[C], av[C];
-#pragma unroll
-  for (int q = 0; q < C; ++q) {
-    sv[q] = st[q < S ? q : S - 1];
-    nv[q] = ns[q < S ? q : S - 1];
-    av[q] = ac[q < A ? q : A - 1];
-  }
-  const float rew = rb.reward[row];
-  const uint8_t dn = rb.done[row];
-#pragma unroll
-  for (int q = 0; q < C; ++q) {
-    if (q < S) {
-      if (s) rlmd_st_wt(s + (int64_t)i * S + q, sv[q]);
-      if (xsa) rlmd_st_wt(xsa + (int64_t)i * X + q, sv[q]);
-      if (s2) rlmd_st_wt(s2 + (int64_t)i * S + q, nv[q]);
-    }
-    if (q < A) {
-      if (a) rlmd_st_wt(a + (int64_t)i * A + q, av[q]);
-      if (xsa) rlmd_st_wt(xsa + (int64_t)i * X + S + q, av[q]);
-    }
-  }
-  if (r) rlmd_st_wt(r + i, rew);
-  if (done) rlmd_st_wt(done + i, dn);
-  if (eff) rlmd_st_wt(eff + i, (int32_t)1);
-  // wider rows (market Dx observations, many-action investors): the rest per chunk
-  for (int k0 = C; k0 < S || k0 < A; k0 += C) {
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const int k = k0 + q;
-      sv[q] = st[k < S ? k : S - 1];
-      nv[q] = ns[k < S ? k : S - 1];
-      av[q] = ac[k < A ? k : A - 1];
-    }
-#pragma unroll
-    for (int q = 0; q < C; ++q) {
-      const int k = k0 + q;
-      if (k < S) {
-        if (s) rlmd_st_wt(s + (int64_t)i * S + k, sv[q]);
-        if (xsa) rlmd_st_wt(xsa + (int64_t)i * X + k, sv[q]);
-        if (s2) rlmd_st_wt(s2 + (int64_t)i * S + k, nv[q]);
-      }
-      if (k < A) {
-        if (a) rlmd_st_wt(a + (int64_t)i * A + k, av[q]);
-        if (xsa) rlmd_st_wt(xsa + (int64_t)i * X + S + k, av[q]);
-      }
-    }
-  }
-}
-
-constexpr int kMaxRounds = 64;
-constexpr int kSortPopulation = 8192;  // M at or below: sort-based subset
+// gather_row1 (single-step rows) and the hash-path draw: rlmd_replay_dev.h, shared
+// with the learner launches that run them as roles (learn.hip agent_learn_k)
+using rlmd::gather_row1;
+using rlmd::kSortPopulation;  // M at or below: sort-based subset
 
 // replay_sample_kernel's explicit arguments as laid out in the kernarg segment
 // (each at its natural alignment, in order): their exact byte count bounds the
@@ -239,40 +180,10 @@ __global__ void __launch_bounds__(kSampleThreads)
     }
     if (i < B) cand[i] = (int64_t)(keys[i] & 0xFFFFFFFFu);
   } else {
-    // rounds of: hash every candidate into an LDS table; the smallest slot per
-    // index owns it (atomicMin: order-independent); the other slots redraw
-    __shared__ unsigned long long tab_key[2 * kSampleThreads];
-    __shared__ int tab_own[2 * kSampleThreads];
-    constexpr int H = 2 * kSampleThreads;
-    if (i < B) {
-      const rlmd_u32x4 v = rlmd_philox(seed, (uint32_t)i, ctr_lo, c2, 0u);
-      cand[i] = (int64_t)rlmd_below(v.x, v.y, (uint64_t)M);
-    }
-    for (int round = 1; round <= kMaxRounds; ++round) {
-      for (int e = i; e < H; e += kSampleThreads) {
-        tab_key[e] = ~0ull;
-        tab_own[e] = 0x7fffffff;
-      }
-      __syncthreads();
-      int h = 0;
-      const unsigned long long c = i < B ? (unsigned long long)cand[i] : 0ull;
-      if (i < B) {
-        h = (int)((c * 0x9E3779B97F4A7C15ull) >> 52) & (H - 1);
-        for (int probe = 0; probe < H; ++probe) {
-          const unsigned long long old = atomicCAS(&tab_key[h], ~0ull, c);
-          if (old == ~0ull || old == c) break;
-          h = (h + 1) & (H - 1);
-        }
-        atomicMin(&tab_own[h], i);
-      }
-      __syncthreads();
-      const bool dup = i < B && tab_own[h] != i;
-      if (dup) {
-        const rlmd_u32x4 v = rlmd_philox(seed, (uint32_t)i, ctr_lo, c2, (uint32_t)round);
-        cand[i] = (int64_t)rlmd_below(v.x, v.y, (uint64_t)M);
-      }
-      if (!__syncthreads_or(dup)) break;
-    }
+    // rounds of hash-table dedupe (rlmd_replay_dev.h replay_draw_hash)
+    __shared__ unsigned long long tab_key[rlmd::kDrawHash];
+    __shared__ int tab_own[rlmd::kDrawHash];
+    rlmd::replay_draw_hash<kSampleThreads>(M, B, seed, ctr_lo, c2, cand, tab_key, tab_own);
   }
   __syncthreads();
   const int per = (B + G - 1) / G;

@@ -2,6 +2,7 @@
 #pragma once
 #include "learn_kernels.h"
 #include "rlmd_adam.h"
+#include "rlmd_replay_dev.h"
 
 namespace rlmd {
 
@@ -24,6 +25,9 @@ struct CritUpdArgs {
   // updates without an actor step (TD3's delayed actor): this update's critic
   // statistics as two extra workgroups of the same launch (B == 0: none)
   LossArgs cstats;
+  // the call's last launch on an update without an actor step: draw.n more
+  // workgroups draw the next call's index sets (learn.hip agent_learn_k)
+  SampleDrawArgs draw;
 };
 
 // The actor (+ temperature) step of one update in one launch
@@ -56,6 +60,8 @@ struct ActUpdArgs {
   // qeval_rows' column split (1 or 2): q and dq/da arrive as P partial sums, at
   // offsets p * B (q) and p * B * A (dq/da)
   int32_t qsplit;
+  // the call's last launch: draw.n more workgroups draw the next call's index sets
+  SampleDrawArgs draw;
 };
 
 size_t critic_update_lds();

@@ -772,6 +772,45 @@ __device__ __forceinline__ void stage_commit(const StageReg& sr, const float* sr
   }
 }
 
+// Staging by index (fwd_rows GATHER): the thread's row index is loaded at kernel
+// start (gidx_load, clamped: branch-free), the ring element once it has landed
+// (stage_issue_g, after the parameter prefetch is issued: that round does not
+// wait on the index).  what 0: next_state, 1: [state | action], 2: state.
+// R * ldx <= NT (the launch checks it): stage_commit's register form.
+__device__ __forceinline__ int64_t gidx_load(const int64_t* idx, int ldx, int row0, int B) {
+  const int r = (int)threadIdx.x / ldx;
+  const int b = row0 + r < B ? row0 + r : B - 1;
+  return idx[b];
+}
+__device__ __forceinline__ StageReg stage_issue_g(const ReplayView& rb, int64_t row, int what, int ldx, int row0,
+                                                  int B) {
+  StageReg sr{0.f, (int)threadIdx.x};
+  const int r = sr.e / ldx, k = sr.e - r * ldx;
+  const int S = rb.S, in = what == 1 ? S + rb.A : S;
+  const bool ok = sr.e < R * ldx && k < in && row0 + r < B;
+  const float* base = what == 0 ? rb.next_state : rb.state;
+  const float* p = base + (ok ? row * S + (k < S ? k : 0) : 0);
+  if (what == 1 && ok && k >= S) p = rb.action + row * rb.A + (k - S);
+  const float v = *p;
+  sr.v = ok ? v : 0.f;
+  return sr;
+}
+// The gather role of fwd_rows GATHER (workgroups past the jobs): mini-batch
+// id / per's rows [64 (id % per), + 64) by index into the slabs, one row per
+// thread of the first wave (replay_sample_kernel's gather, G = per parts).
+__device__ __forceinline__ void gather_role(const HoistGatherArgs& g, int id, int B) {
+  const int per = (B + kGatherRows - 1) / kGatherRows;
+  if (id >= g.nk * per || (int)threadIdx.x >= kGatherRows) return;
+  const int k = id / per, i = (id - k * per) * kGatherRows + (int)threadIdx.x;
+  if (i >= B) return;
+  const int S = g.rb.S, A = g.rb.A;
+  const int64_t o = (int64_t)k * B;
+  const int64_t row = g.idx[o + i];
+  g.o_idx[o + i] = row;
+  gather_row1(g.rb, row, i, g.o_s + o * S, g.o_a + o * A, g.o_r + o, g.o_s2 + o * S, g.o_done + o,
+              g.o_xsa + o * (S + A), nullptr);
+}
+
 template <int NBW>
 __device__ __forceinline__ void actor_const(FwdConst<NBW>& k, const RowNet& n, const NetOff& ao, const RowDims& d) {
   const bool sac = d.algo == RLMD_SAC;
@@ -812,7 +851,9 @@ __device__ __forceinline__ void basis_pass(Pre<PREC, NBW, MULTI>& pw, const type
 // y = 0, 1: target path with target critic y (the policy sample is recomputed
 // per critic: same Philox draws, the logp written once); y = 2, 3: online
 // critic y - 2 on (s, a); y = 4: policy on s for the actor step.
-template <int PREC, int NBW, bool MULTI>
+// GATHER (update 0 of a call with index sets drawn ahead, a.hg): rows staged from
+// the ring by index; grid rows y past the jobs run the gather role.
+template <int PREC, int NBW, bool MULTI, bool GATHER = false>
 __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
   RLMD_KERNARG_PREFETCH(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -824,6 +865,13 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
   // jobs y0 .. nj - 1 of this update, then (npair) the next update's target jobs
   const int nj = a.with_actor ? 5 : 4;
   int job = (int)blockIdx.y + a.y0;
+  if constexpr (GATHER) {
+    const int nyj = nj - a.y0 + 2 * a.npair;
+    if ((int)blockIdx.y >= nyj) {
+      if (blockIdx.z == 0) gather_role(a.hg, ((int)blockIdx.y - nyj) * (int)gridDim.x + (int)blockIdx.x, d.B);
+      return;
+    }
+  }
   const bool nxt = job >= nj;
   if (nxt) job -= nj;
   const bool sac = d.algo == RLMD_SAC;
@@ -848,7 +896,10 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     const float* eps_next = nxt ? nullptr : a.eps_next;
     SampleCfg smp = a.smp;
     if (nxt) smp.ctr = a.ctrn;  // the next update's learn_step_cntr (its target noise draws)
-    const StageReg sr = stage_issue(s2, d.S, L.ldx, row0, B);
+    int64_t grow = 0;
+    StageReg sr{};
+    if constexpr (GATHER) grow = gidx_load(a.hg.idx + (nxt ? B : 0), L.ldx, row0, B);
+    else sr = stage_issue(s2, d.S, L.ldx, row0, B);
     const HeadBias hb = head_bias(an.p, a.ao, d);
     const bool pre_nz = eps_next == nullptr;
     FwdConst<NBW> ka, kc;
@@ -862,6 +913,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
       pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
     };
     if constexpr (!RLMD_FWD_DEFER) issue_critic();
+    if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 0, L.ldx, row0, B);
     const Noise2 nz = pre_nz ? noise_pre(smp, d, a.t_tag, row0) : Noise2{{0.f, 0.f}};
     RLMD_TSR(16 * job + 1);
     stage_commit(sr, s2, d.S, xs, L.ldx, row0, B);
@@ -897,11 +949,15 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     const int g = job - 2;
     const RowNet& cn = a.crit[g];
     const bool upd = a.u1[0] != nullptr;
-    const StageReg sr = stage_issue(a.xsa, d.X, L.ldx, row0, B);
+    int64_t grow = 0;
+    StageReg sr{};
+    if constexpr (GATHER) grow = gidx_load(a.hg.idx, L.ldx, row0, B);
+    else sr = stage_issue(a.xsa, d.X, L.ldx, row0, B);
     FwdConst<NBW> kc;
     critic_const<NBW>(kc, cn, a.co, d, nb0);
     Pre<PREC, NBW, MULTI> pc, pw;
     pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
+    if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 1, L.ldx, row0, B);
     // the basis pass's stream (the transposed copy): after the forward's layer 2
     auto issue_basis = [&] {
       if (upd) pre_issue<PREC, NBW, MULTI>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0);
@@ -939,12 +995,16 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
   } else {  // policy on s for the actor update (algo_sac.py:524-535 / algo_td3.py:507-515)
     RLMD_TSR(80);
     const RowNet& an = a.actor;
-    const StageReg sr = stage_issue(a.s, d.S, L.ldx, row0, B);
+    int64_t grow = 0;
+    StageReg sr{};
+    if constexpr (GATHER) grow = gidx_load(a.hg.idx, L.ldx, row0, B);
+    else sr = stage_issue(a.s, d.S, L.ldx, row0, B);
     const HeadBias hb = head_bias(an.p, a.ao, d);
     FwdConst<NBW> ka;
     actor_const<NBW>(ka, an, a.ao, d);
     Pre<PREC, NBW, MULTI> pa;
     pre_issue<PREC, NBW, MULTI>(pa, an.wc, H1p, H1p, H2p / 16);
+    if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 2, L.ldx, row0, B);
     const bool pre_nz = a.eps_cur == nullptr && a.a_mode == 0;
     const Noise2 nz = pre_nz ? noise_pre(a.smp, d, a.a_tag, row0) : Noise2{{0.f, 0.f}};
     stage_commit(sr, a.s, d.S, xs, L.ldx, row0, B);
@@ -1612,6 +1672,11 @@ void launch_kind(int kind, const void* args, dim3 grid, size_t lds, hipStream_t 
       hipLaunchKernelGGL((fwd_rows_kernel<PREC, NBW, MULTI>), grid, dim3(NT), lds, st,
                          *static_cast<const FwdRowsArgs*>(args));
       break;
+    case 4:  // fwd_rows staging by index (bf16 only: the hoisted sample path)
+      if constexpr (PREC == RLMD_BF16)
+        hipLaunchKernelGGL((fwd_rows_kernel<PREC, NBW, MULTI, true>), grid, dim3(NT), lds, st,
+                           *static_cast<const FwdRowsArgs*>(args));
+      break;
     case 1:
       hipLaunchKernelGGL((qeval_rows_kernel<PREC, NBW, MULTI>), grid, dim3(NT), lds, st,
                          *static_cast<const QEvalArgs*>(args));
@@ -1681,7 +1746,18 @@ int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split) {
   RLMD_CHECK(a.npair == 0 || (a.y0 == 0 && a.s2n && a.qtn[0] && a.qtn[1]), "fwd_rows: target pairing buffers");
   RLMD_CHECK(split == 1 || (split == 2 && a.u1[0] && a.d.H2p % 64 == 0),
              "fwd_rows: a column split needs the fused critic path and H2p a multiple of 64");
-  return launch_rows(a.d, 0, &a, (a.with_actor ? 5 : 4) - a.y0 + 2 * a.npair, st, 0, split);
+  const int ny = (a.with_actor ? 5 : 4) - a.y0 + 2 * a.npair;
+  if (a.hg.idx) {
+    RLMD_CHECK(a.d.prec == RLMD_BF16 && R * lds_layout(a.d).ldx <= NT && a.hg.rb.n_steps <= 1 && a.hg.nk >= 1 &&
+                   (a.npair == 0 || a.hg.nk >= 2) && a.eps_next == nullptr && a.eps_cur == nullptr,
+               "fwd_rows: staging by index takes bf16, single-step rows up to 32 wide");
+    return launch_rows(a.d, 4, &a, ny + fwd_rows_gather_y(a.d.B, a.hg.nk), st, 0, split);
+  }
+  return launch_rows(a.d, 0, &a, ny, st, 0, split);
+}
+int fwd_rows_gather_y(int B, int nk) {
+  const int nrb = (B + R - 1) / R, per = (B + kGatherRows - 1) / kGatherRows;
+  return (nk * per + nrb - 1) / nrb;
 }
 int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split) {
   RLMD_CHECK(a.nq == nq && (a.nab == 0 || (a.ua && a.wheads && a.am1 && a.am2)), "qeval_rows: head jobs need their buffers");

@@ -258,6 +258,11 @@ __global__ void __launch_bounds__(NT) critic_update_kernel(CritUpdArgs a) {
   // per critic: fc2.weight tiles, fc1 blocks, then head workgroups (b2 / w3 of 32
   // fc2 rows each, b3 on the first)
   const int per = a.n_w2 + a.n_w1 + a.ti;
+  // the last draw.n workgroups: the next call's index draw (rlmd_replay_dev.h)
+  if (a.draw.n > 0 && blockIdx.x >= gridDim.x - a.draw.n) {
+    replay_draw_role<NT>(a.draw, (int)(blockIdx.x - (gridDim.x - a.draw.n)), smem);
+    return;
+  }
   if ((int)blockIdx.x >= 2 * per) {
     // the critic statistics of an update without an actor step (rlmd_loss.h), beside
     // the step: they read the loss scalars' starting slot, part 0 writes the other
@@ -636,6 +641,11 @@ __global__ void __launch_bounds__(NT) actor_update_kernel(ActUpdArgs a) {
   // roles as in critic_update_kernel: tiles, fc1 blocks, head workgroups, then the
   // two critic-statistics workgroups (handled in the body's first branch)
   const int t = blockIdx.x;
+  // the last draw.n workgroups: the next call's index draw (rlmd_replay_dev.h)
+  if (a.draw.n > 0 && blockIdx.x >= gridDim.x - a.draw.n) {
+    replay_draw_role<NT>(a.draw, (int)(blockIdx.x - (gridDim.x - a.draw.n)), smem);
+    return;
+  }
 #if RLMD_ROLE_SPLIT
   if (t < a.n_w2) actor_update_body<PREC, kRoleW2>(a, smem);
   else if (t < a.n_w2 + a.n_w1) actor_update_body<PREC, kRoleW1>(a, smem);
@@ -1104,6 +1114,8 @@ extern "C" int rlmd_debug_ts_aupd(unsigned long long* out) {
 }
 #endif
 
+static_assert(DrawLds::total <= ULds::total && DrawLds::total <= ALds::total, "the draw role fits the update kernels' LDS");
+
 size_t critic_update_lds() { return (size_t)ULds::total; }
 int actor_update_n_w1(const RowDims& d) { return d.H1p / TW1; }
 int critic_update_tj(const RowDims& d) { return d.B <= 256 ? (d.H1p / TW + 1) / 2 : d.H1p / TW; }
@@ -1115,7 +1127,9 @@ int actor_update_launch(const ActUpdArgs& a, hipStream_t st) {
                  d.H1p % TW1 == 0,
              "actor update: tile grid inconsistent with the widths");
   RLMD_CHECK(a.cstats.B <= NT, "critic statistics workgroup: mini-batch up to 512 rows");
-  const dim3 grid(a.n_w2 + a.n_w1 + a.ti + (a.cstats.B > 0 ? 2 : 0));
+  RLMD_CHECK(a.draw.n == 0 || (a.draw.idx_out && a.draw.B <= RLMD_MAX_BATCH && a.draw.M > kSortPopulation),
+             "actor update: the draw role takes the hash path only");
+  const dim3 grid(a.n_w2 + a.n_w1 + a.ti + (a.cstats.B > 0 ? 2 : 0) + a.draw.n);
   if (d.prec == RLMD_BF16)
     hipLaunchKernelGGL(actor_update_kernel<RLMD_BF16>, grid, dim3(NT), ALds::total, st, a);
   else
@@ -1132,7 +1146,9 @@ int critic_update_launch(const CritUpdArgs& a, hipStream_t st) {
   RLMD_CHECK(a.tj == critic_update_tj(d) && a.ti * TW >= d.H2p && a.n_w2 == a.ti * a.tj && a.n_w1 == d.H1p / TW,
              "critic update: tile grid inconsistent with the widths");
   RLMD_CHECK(a.cstats.B <= NT, "critic statistics workgroups: mini-batch up to 512 rows");
-  const dim3 grid(2 * (a.n_w2 + a.n_w1 + a.ti) + (a.cstats.B > 0 ? 2 : 0));
+  RLMD_CHECK(a.draw.n == 0 || (a.draw.idx_out && a.draw.B <= RLMD_MAX_BATCH && a.draw.M > kSortPopulation),
+             "critic update: the draw role takes the hash path only");
+  const dim3 grid(2 * (a.n_w2 + a.n_w1 + a.ti) + (a.cstats.B > 0 ? 2 : 0) + a.draw.n);
   const bool split = !RLMD_SPLIT_SPEC || a.loss.qsplit > 1;
 #define CRIT_LAUNCH(P_, W_)                                                                                  \
   do {                                                                                                       \
