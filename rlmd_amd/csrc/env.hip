@@ -4,32 +4,14 @@
 // steps one lane (the work per lane is ~100 FP64 ops and a few dozen bytes, so
 // the kernel is HBM/latency bound: SoA lane state, coalesced f32/f64 arrays).
 //
-// Reference semantics restated (file:line into majidsina/rlmd):
-//   coin   envs/coin_flip_envs.py:150-216 (A), :290-362 (B, stop-loss = |a0| :308),
-//          :436-521 (C); consts :40-93
-//   dice   envs/dice_roll_envs.py:153-219, :293-365, :439-524; consts :39-96
-//   gbm    envs/gbm_envs.py:147-212, :286-357, :431-515; consts :43-90
-//   dice_sh envs/dice_roll_sh_envs.py:160-235 (INSURED), :290-365, :420-502, :557-645
-//   market envs/market_envs.py:133-202 (D1), :611-682 (Dx) + B/C variants
-//   dones  tools/env_resources.py:26-80 (any lev_max), :83-137 (all), :140-200 (market)
-//   slicing tools/env_resources.py:203-291 (observed_market_state/time_slice/shuffle_data)
-//
-// Precision follows the reference's dtype flow under NumPy 2 for f32 actions
-// (restated and pinned bit-exactly in oracle/envs.py): wealth and
-// returns f64; GBM / market leverages f32 (`f32 * Python int`), coin / dice
-// leverages f64 (`f32 * np.float64`); stop-loss, retention, safe-haven leverage,
-// `1e4 * stop_loss`, `max(., MIN_VALUE)` and the first-step bet size f32;
-// Dice_SH_INSURED leverage f32.  FP contraction is off so every rounding
-// happens where NumPy's does.
+// The lane model (the reference's semantics and dtype flow restated) is rlmd_env_lane.h; here
+// are the kernels, the host dispatch and the C ABI.  FP contraction is off, as there.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stdlib.h>
 #include <stddef.h>
 #include <string.h>
 #include <hip/hip_ext.h>
-
-#include <algorithm>
-#include <vector>
 
 #include "../../include/rlmd_abi.h"
 #include "learn_kernels.h"
@@ -49,33 +31,9 @@ __device__ unsigned long long g_ts_actenv[4096][8];
 #include "rlmd_act_rows.h"
 #include "rlmd_common.h"
 #include "rlmd_internal.h"
+#include "rlmd_env_lane.h"
 
 namespace {
-
-constexpr double kInitialValue = 1e4;
-constexpr double kMinValue = 100.0;  // max(MIN_VALUE_RATIO * INITIAL_VALUE, 1)
-constexpr double kMaxAbsAction = 0.99;
-constexpr double kMinWeight = 1e-5;
-
-struct FamConst {
-  double max_value, min_reward, min_return, max_return, lev_factor;
-};
-
-__host__ __device__ constexpr FamConst fam_const(int fam) {
-  switch (fam) {
-    case RLMD_COIN: return {1e18, 1e-3, -0.9, 1e10, 2.0};
-    case RLMD_DICE: return {1e18, 1e-3, -0.9, 1e10, 2.0};
-    case RLMD_GBM: return {1e18, 1e-3, -2.3025850929940455 /* np.log(0.1) */, 1e10, 5.0};
-    case RLMD_DICE_SH: return {1e18, 1e-6, -0.99, 1e10, 2.0};
-    default: return {1e34, 1e-3, -0.9, 1e10, 3.0};
-  }
-}
-
-// GBM: LOG_MEAN = DRIFT - VOL**2 / 2 (envs/gbm_envs.py:43-63)
-constexpr double kGbmDrift = 0.0540025395205692;
-constexpr double kGbmVol = 0.1897916175617430;
-// dice_sh: I_LEV_FACTOR = (-1 - 5) / (-0.5 - 5) (envs/dice_roll_sh_envs.py:70)
-constexpr double kShILev = (-1.0 - 5.0) / (-0.5 - 5.0);
 
 #ifdef RLMD_TIMING
 // experiment builds only (tools/ts_probe.py env): per-workgroup s_memrealtime at
@@ -92,376 +50,8 @@ __device__ unsigned long long g_ts_env[2048][8];
   } while (0)
 #endif
 
-struct EnvParams {
-  int fam, inv, n_lanes, n, obs_days, time_length, action_days, shuffle_days;
-  int state_dim, action_dim, risk_dim, draw_dim, ext_len, start_range, n_days;
-  int slice_groups;  // market: lanes sharing slice draws in groups (lane % G; 0 = per lane)
-  // replay rows store s = s' from an episode's second step on: the reference's
-  // coin / dice / GBM / market envs return one self.next_state array mutated in
-  // place (e.g. gbm_envs.py:125, 184-186, 212), its loop keeps state = next_state
-  // (rl_multiplicative.py:245, rl_market.py:273) and stores state after the
-  // next env.step (:218-220; replay.py:164-167 copies then); reset() returns a
-  // fresh array (gbm_envs.py:224-229), so an episode's first row keeps the reset
-  // state.  Dice_SH builds a new array per step (dice_roll_sh_envs.py:336): 0.
-  int alias_state;
-  uint64_t seed;
-  const double* prices;  // market [n_days, n]
-  // lane state
-  double* wealth;
-  int32_t* time;
-  int32_t* start;
-  uint32_t* episode;
-  // per-episode log of the fused train step (nullable): one region of ep_cap
-  // rows [step, lane, final reward, length, risk...] (ep_w floats) per wave,
-  // ep_cnt[wave] = rows appended since the last drain (counts past ep_cap too)
-  float* ep_rows;
-  uint32_t* ep_cnt;
-  int ep_cap, ep_w;
-};
-
-// --- categorical outcome from a uniform: NumPy legacy choice(a, p) =
-// a[searchsorted(cumsum(p)/cumsum(p)[-1], u, 'right')] (pinned by tests/golden/rng_kat.npz).
-__device__ __host__ inline double coin_outcome(double u) {
-  const double c0 = 0.5, c1 = 0.5 + 0.5;
-  const int idx = (c0 / c1 <= u) + (c1 / c1 <= u);
-  return idx == 0 ? 0.5 : -0.4;
-}
-__device__ __host__ inline int dice_index(double u) {
-  const double p0 = 1.0 / 6.0, p1 = 1.0 / 6.0, p2 = 1.0 - (1.0 / 6.0 + 1.0 / 6.0);
-  const double c0 = p0, c1 = c0 + p1, c2 = c1 + p2;
-  return (c0 / c2 <= u) + (c1 / c2 <= u) + (c2 / c2 <= u);
-}
-__device__ __host__ inline double dice_value(int idx) {
-  return idx == 0 ? 0.5 : (idx == 1 ? -0.5 : 0.05);
-}
-
-// Fisher–Yates permutation of a block of `bs` (<= 16) rows for market shuffles.
-// The permutation lives in one 64-bit register as 16 four-bit entries (no
-// per-thread array, hence no scratch).
-__device__ inline int market_perm(uint64_t seed, uint32_t lane, uint32_t ep, uint32_t blk, int bs,
-                                  int pos) {
-  uint64_t p = 0xFEDCBA9876543210ull;  // entry i = i
-  rlmd_u32x4 w = {0, 0, 0, 0};
-  for (int i = bs - 1, k = 0; i >= 1; --i, ++k) {
-    if ((k & 3) == 0) w = rlmd_philox(seed, lane, ep, RLMD_TAG_MKT_PERM, blk * 4u + (k >> 2));
-    const uint32_t word = (k & 3) == 0 ? w.x : (k & 3) == 1 ? w.y : (k & 3) == 2 ? w.z : w.w;
-    const int j = (int)(((uint64_t)word * (uint64_t)(i + 1)) >> 32);
-    const uint64_t pi = (p >> (4 * i)) & 15u, pj = (p >> (4 * j)) & 15u;
-    p &= ~((15ull << (4 * i)) | (15ull << (4 * j)));
-    p |= (pj << (4 * i)) | (pi << (4 * j));
-  }
-  return (int)((p >> (4 * pos)) & 15u);
-}
-
-// the Philox counter of a lane's market slice draws (start row, block shuffles)
-__device__ inline uint32_t slice_key(const EnvParams& P, uint32_t lane) {
-  return P.slice_groups > 0 ? lane % (uint32_t)P.slice_groups : lane;
-}
-
-// source price row of extract row e (time_slice + shuffle_data)
-__device__ inline int market_row(const EnvParams& P, uint32_t lane, int start, uint32_t ep, int e) {
-  const int D = P.shuffle_days;
-  if (D <= 1) return start + e;
-  const int full = P.ext_len / D, blk = e / D, within = e % D;
-  const int bs = blk < full ? D : P.ext_len - full * D;
-  return start + blk * D + market_perm(P.seed, slice_key(P, lane), ep, (uint32_t)blk, bs, within);
-}
-
-// observed_market_state element k (tools/env_resources.py:203-226): D1 -> row t*ad
-// asset k; Dx -> rows [t*ad, t*ad+d) flattened then reversed.
-__device__ inline double market_obs(const EnvParams& P, uint32_t lane, int start, uint32_t ep,
-                                    int t, int k) {
-  int row, asset;
-  if (P.obs_days == 1) {
-    row = t * P.action_days;
-    asset = k;
-  } else {
-    const int f = P.obs_days * P.n - 1 - k;
-    row = t * P.action_days + f / P.n;
-    asset = f % P.n;
-  }
-  return P.prices[(int64_t)market_row(P, lane, start, ep, row) * P.n + asset];
-}
-
-// np.sum / np.mean of a small array: NumPy's pairwise_sum for n <= 128
-// (sequential below 8 elements, 8 accumulators otherwise).
-template <typename T, typename GetF>
-__device__ inline T np_sum(int n, GetF get) {
-  T res;
-  if (n < 8) {
-    res = (T)0;
-    for (int i = 0; i < n; ++i) res += get(i);
-  } else {
-    T r[8];
-    for (int k = 0; k < 8; ++k) r[k] = get(k);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int k = 0; k < 8; ++k) r[k] += get(i + k);
-    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += get(i);
-  }
-  return res;
-}
-template <typename T, typename GetF>
-__device__ inline T np_mean(int n, GetF get) {
-  return np_sum<T>(n, get) / (T)n;
-}
-
-
-struct StepOut {
-  double W, reward;
-  bool done, learn_done;
-};
-
-struct NoDoneHook {
-  __device__ void operator()(const StepOut&) const {}
-};
-
-// market: the action-independent relative prices obs(t, k) / obs(0, k) - 1 of a
-// step, when a caller has them precomputed (kOn); otherwise read in the step
-struct NoMrel {
-  static constexpr bool kOn = false;
-  __device__ double operator()(int) const { return 0.0; }
-};
-struct MrelRow {
-  static constexpr bool kOn = true;
-  const double* row;
-  __device__ double operator()(int k) const { return row[k]; }
-};
-
-// One env step for one lane.  `act(i)` yields action i as AT, `draw(j)` the
-// j-th uniform/normal.  Writes state element k through st(k, v) and risk
-// element k through rk(k, v).
-// AT is the dtype of the action array the reference's env.step receives: f32
-// from the policy / warm-up sampler, f64 inside the smoothing window (np.clip
-// with np.float64 bounds promotes, utils.py:345-373).  Every action-derived
-// quantity follows NumPy 2's promotion from it: with f32 actions, GBM/market
-// leverage (x Python int) and the half-shifted stop-loss / retention / safe-haven
-// weights stay f32; with f64 actions everything is f64.
-//
-// FAM (the env family) is a template parameter, so each family's kernel holds
-// only its own code; NG > 0 fixes n_gambles / n_assets at compile time (the
-// n == 1 configurations), NG == 0 reads it from P.
-template <int FAM, int NG, typename AT, typename ActF, typename DrawF, typename StF, typename RkF,
-          typename DoneF = NoDoneHook, typename MrelF = NoMrel>
-__device__ inline StepOut env_step_lane(const EnvParams& P, uint32_t lane, double w0, int t,
-                                        int start, uint32_t ep, ActF act, DrawF draw, StF st,
-                                        RkF rk, DoneF on_done = DoneF{}, MrelF mrel = MrelF{}) {
-  constexpr FamConst C = fam_const(FAM);
-  constexpr int fam = FAM;
-  const int inv = P.inv, n = NG ? NG : P.n;
-  const bool use_all = (fam == RLMD_GBM || fam == RLMD_MARKET);  // lev_max: np.all (Q4)
-  const bool f32lev = use_all && sizeof(AT) == 4;                // lev = f32 action * int
-  const double lev_cap64 = kMaxAbsAction * C.lev_factor;
-  const float lev_cap32 = (float)lev_cap64;
-  auto half_shift = [](AT a) -> AT { return (a + (AT)kMaxAbsAction) / (AT)2; };
-
-  AT sl32 = (AT)NAN, ret32 = (AT)NAN, lev_sh32 = (AT)NAN;
-  double R = 0.0, lev_mean = 0.0, lev0 = 0.0, r_sh = 0.0, r_die = 0.0;
-  bool lev_max_any = false, lev_max_all = true, lev_min_all = true;
-  int lev_off = 0;
-
-  if (fam == RLMD_DICE_SH) {
-    const int idx = dice_index(draw(0));
-    r_die = dice_value(idx);
-    r_sh = idx == 2 ? -0.99 : (idx == 0 ? -0.99 : 5.0);  // MID, UP -> -0.99 ; DOWN -> 5
-    double lev;
-    if (inv == RLMD_INV_INSURED) {
-      const AT lev32 = act(0) * (AT)kShILev;  // action * Python float
-      lev = (double)lev32;
-      lev_sh32 = (AT)1 - lev32;
-      lev_min_all = fabs(lev32) < (AT)kMinWeight;
-    } else {
-      const int ai = inv == RLMD_INV_A ? 0 : (inv == RLMD_INV_B ? 1 : 2);
-      if (inv != RLMD_INV_A) sl32 = half_shift(act(0));
-      if (inv == RLMD_INV_C) ret32 = half_shift(act(1));
-      lev = (double)act(ai) * C.lev_factor;
-      lev_sh32 = half_shift(act(ai + 1)) * (AT)1;
-      lev_min_all = fabs(lev) < kMinWeight;
-    }
-    lev_max_any = fabs(lev) == lev_cap64;
-    R = lev * r_die + (double)(lev_sh32 * (AT)r_sh);
-    lev_mean = lev;
-    lev0 = lev;
-  } else {
-    if (inv == RLMD_INV_B) {
-      sl32 = fam == RLMD_COIN ? (AT)fabs(act(0)) : half_shift(act(0));  // Coin_InvB: |a0| (Q1)
-      lev_off = 1;
-    } else if (inv == RLMD_INV_C) {
-      sl32 = half_shift(act(0));
-      ret32 = half_shift(act(1));
-      lev_off = 2;
-    }
-    auto ret_of = [&](int j) -> double {
-      if (fam == RLMD_COIN) return coin_outcome(draw(j));
-      if (fam == RLMD_DICE) return dice_value(dice_index(draw(j)));
-      if (fam == RLMD_GBM) return (kGbmDrift - kGbmVol * kGbmVol / 2) + kGbmVol * draw(j);
-      if constexpr (MrelF::kOn) return mrel(j);
-      return market_obs(P, lane, start, ep, t, j) / market_obs(P, lane, start, ep, 0, j) - 1.0;
-    };
-    auto lev_of = [&](int j) -> double {
-      const AT a = act(lev_off + j);
-      return f32lev ? (double)((float)a * (float)C.lev_factor) : (double)a * C.lev_factor;
-    };
-    R = np_sum<double>(n, [&](int j) { return lev_of(j) * ret_of(j); });  // np.sum(lev * r)
-    for (int j = 0; j < n; ++j) {
-      const AT a = act(lev_off + j);
-      if (f32lev) {
-        const float l32 = (float)a * (float)C.lev_factor;
-        lev_max_all &= fabsf(l32) == lev_cap32;
-        lev_min_all &= fabsf(l32) < (float)kMinWeight;
-      } else {
-        const double lev = (double)a * C.lev_factor;
-        lev_max_all &= fabs(lev) == lev_cap64;
-        lev_max_any |= fabs(lev) == lev_cap64;
-        lev_min_all &= fabs(lev) < kMinWeight;
-      }
-    }
-    lev0 = lev_of(0);
-    if (f32lev)
-      lev_mean = (double)np_mean<float>(n, [&](int j) { return (float)act(lev_off + j) * (float)C.lev_factor; });
-    else
-      lev_mean = np_mean<double>(n, [&](int j) { return (double)act(lev_off + j) * C.lev_factor; });
-  }
-
-  // one-step return and growth factor
-  double g;
-  if (fam == RLMD_GBM) {
-    R = fmax(R, C.min_return);
-    g = fmin(exp(R), 1.0 + C.max_return);
-  } else {
-    R = fmin(fmax(R, C.min_return), C.max_return);
-    g = 1.0 + R;
-  }
-
-  double W, mw;
-  bool done_active = false;
-  if (inv == RLMD_INV_A || inv == RLMD_INV_INSURED) {
-    mw = kMinValue;
-    W = fmin(fmax(w0 * g, kMinValue), C.max_value);
-  } else {
-    const AT mw32 = fmax((AT)kInitialValue * sl32, (AT)kMinValue);
-    if (inv == RLMD_INV_C && w0 > kInitialValue)
-      mw = kInitialValue + (w0 - kInitialValue) * (double)ret32;
-    else
-      mw = (double)mw32;
-    // episode's first step: wealth is still the Python float 1e4 -> f32 subtraction
-    const double active = t == 1 ? (double)fmax((AT)kInitialValue - mw32, (AT)0) : fmax(w0 - mw, 0.0);
-    W = fmin(fmax(mw + active * g, mw), C.max_value);
-    done_active = active == 0.0;
-  }
-  const double growth = W / kInitialValue;
-  const double reward = exp(log(growth) / (double)t);
-
-  // next state / MAX_VALUE (and done_state = any(next_state >= 1))
-  bool done_state = false;
-  auto put = [&](int k, double v) {
-    const double s = v / C.max_value;
-    done_state |= s >= 1.0;
-    st(k, s);
-  };
-  put(0, W);
-  put(1, R);
-  put(2, growth);
-  put(3, reward);
-  if (fam == RLMD_DICE_SH) {
-    put(4, r_die);
-    put(5, r_sh);
-  } else if (fam == RLMD_MARKET) {
-    const int m = P.obs_days * n;
-    for (int k = 0; k < m; ++k)
-      put(4 + k, MrelF::kOn ? mrel(k)
-                            : market_obs(P, lane, start, ep, t, k) / market_obs(P, lane, start, ep, 0, k) - 1.0);
-  } else {
-    for (int j = 0; j < n; ++j) {
-      double r;
-      if (fam == RLMD_COIN) r = coin_outcome(draw(j));
-      else if (fam == RLMD_DICE) r = dice_value(dice_index(draw(j)));
-      else r = (kGbmDrift - kGbmVol * kGbmVol / 2) + kGbmVol * draw(j);
-      put(4 + j, r);
-    }
-  }
-
-  const bool lev_max = use_all ? lev_max_all : lev_max_any;
-  const bool done_time = fam == RLMD_MARKET &&
-                         t == (P.obs_days == 1 ? P.time_length : P.time_length - P.obs_days + 1);
-  const bool done = done_time || W == mw || reward < C.min_reward || R == C.min_return || lev_max ||
-                    lev_min_all || done_state || done_active;
-  StepOut o;
-  o.W = W;
-  o.reward = reward;
-  o.done = done;
-  o.learn_done = done && !done_state && !done_time;
-  on_done(o);  // the done flags are known before the risk vector is emitted
-
-  // risk vector
-  rk(0, reward);
-  rk(1, W);
-  rk(2, R);
-  if (fam == RLMD_DICE_SH) {
-    rk(3, lev0);
-    rk(4, (double)sl32);
-    rk(5, (double)ret32);
-    rk(6, (double)lev_sh32);
-  } else {
-    rk(3, lev_mean);
-    int k = 4;
-    if (inv == RLMD_INV_B || inv == RLMD_INV_C) rk(k++, (double)sl32);
-    if (inv == RLMD_INV_C) rk(k++, (double)ret32);
-    if (n > 1) {
-      for (int j = 0; j < n; ++j) {
-        const AT a = act(lev_off + j);
-        rk(k + j, f32lev ? (double)((float)a * (float)C.lev_factor) : (double)a * C.lev_factor);
-      }
-    }
-  }
-  return o;
-}
-
-// draws for gamble j: Philox(seed, lane, step, ENV_DRAW, j/2), two per block
-template <int FAM>
-__device__ inline double philox_draw(const EnvParams& P, uint32_t lane, uint32_t step, int j) {
-  const rlmd_u32x4 v = rlmd_philox(P.seed, lane, step, RLMD_TAG_ENV_DRAW, (uint32_t)(j >> 1));
-  if (FAM == RLMD_GBM) {
-    double z0, z1;
-    rlmd_normal2(v, z0, z1);
-    return (j & 1) ? z1 : z0;
-  }
-  return (j & 1) ? rlmd_u01(v.z, v.w) : rlmd_u01(v.x, v.y);
-}
-
-// reset one lane: episode start (market: new slice), state element writer
-// start_at >= 0 (market): the episode's first price row is given (eval_market's
-// gap index) instead of drawn.
-// ep_now >= 0: the lane's current episode counter, already in a register (the
-// training step's epilogue loaded it with the lane state; re-reading it here put
-// a dependent global load into the tail of every wave with a finished lane).
-template <int FAM, typename StF>
-__device__ inline void env_reset_lane(const EnvParams& P, uint32_t lane, StF st, int start_at = -1,
-                                      int64_t ep_now = -1) {
-  P.wealth[lane] = kInitialValue;
-  P.time[lane] = 1;
-  const uint32_t ep = (ep_now >= 0 ? (uint32_t)ep_now : P.episode[lane]) + 1;
-  P.episode[lane] = ep;
-  constexpr FamConst C = fam_const(FAM);
-  st(0, kInitialValue / C.max_value);
-  st(1, 0.0);
-  st(2, 1.0 / C.max_value);
-  st(3, 1.0 / C.max_value);
-  if (FAM == RLMD_MARKET) {
-    const rlmd_u32x4 v = rlmd_philox(P.seed, slice_key(P, lane), ep, RLMD_TAG_MKT_START, 0);
-    const int start = start_at >= 0 ? start_at : (int)rlmd_below(v.x, v.y, (uint64_t)P.start_range);
-    P.start[lane] = start;
-    const int m = P.obs_days * P.n;
-    for (int k = 0; k < m; ++k)
-      st(4 + k, P.obs_days == 1 ? 0.0 : market_obs(P, lane, start, ep, 0, k) / C.max_value);
-  } else {
-    for (int k = 4; k < P.state_dim; ++k) st(k, 0.0);
-  }
-}
-
 // Finished-episode statistics of the fused train step: each launch writes one
-// row {episodes, sum of final rewards, sum of lengths, 0} per workgroup into
+// row {episodes, sum of final rewards, sum of lengths, -} per 64 lanes into
 // part_out; the next launch's block 0 (or rlmd_train_flush_stats) adds the
 // rows of fold_src into the caller's f64[4] accumulator fold_dst.
 struct StatFold {
@@ -478,10 +68,13 @@ struct StatFold {
 __device__ inline void fold_stat_rows(const double* src, int rows, double* dst, double (*fr)[256]) {
   const int i = threadIdx.x;
   double a = 0.0, b = 0.0, c = 0.0;
-  for (int r = i; r < rows; r += blockDim.x) {
-    a += src[(int64_t)r * 4 + 0];
-    b += src[(int64_t)r * 4 + 1];
-    c += src[(int64_t)r * 4 + 2];
+  for (int r = i; r < rows; r += 4 * blockDim.x) {  // four rounds of loads in flight; the sums keep their order
+    double v[4][3];
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+      v[k / 3][k % 3] = r + k / 3 * blockDim.x < rows ? src[(int64_t)(r + k / 3 * blockDim.x) * 4 + k % 3] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a += v[k][0], b += v[k][1], c += v[k][2];
   }
   fr[0][i] = a;
   fr[1][i] = b;
@@ -541,8 +134,6 @@ __global__ void __launch_bounds__(256) env_step_kernel(EnvParams P, uint32_t ste
   done[2 * lane + 1] = o.learn_done;
 }
 
-// Upper bound of the action count when it is known at compile time (dice_sh:
-// <= 4; NG > 0: NG + 2 for InvC), else 0 (read through memory per use).
 // ring row of a lane: the host hands ring_base already reduced mod capacity, so
 // one conditional subtract replaces the 64-bit remainder (a long software
 // sequence on the lane's critical path); rings smaller than the lane count wrap
@@ -553,8 +144,113 @@ __device__ __forceinline__ int64_t ring_row(int64_t base, int64_t lane, int64_t 
   return r;
 }
 
+// Upper bound of the action count when it is known at compile time (dice_sh:
+// <= 4; NG > 0: NG + 2 for InvC), else 0 (read through memory per use).
 template <int FAM, int NG>
 constexpr int kActRegs = FAM == RLMD_DICE_SH ? 4 : (NG > 0 ? NG + 2 : 0);
+
+// the action array env.step receives, from the f64 value v: the exact f32 of a
+// policy action outside the smoothing window, else np.clip with f64 bounds
+template <typename AT>
+__device__ __forceinline__ AT window_action(double v, double lo, double hi) {
+  return sizeof(AT) == 4 ? (AT)v : (AT)fmin(fmax(v, lo), hi);
+}
+
+// ---- what follows env_step_lane in a training step (env_train_kernel, act_env_kernel)
+// env_step_lane's on_done hook: finished lanes of this wave take consecutive rows
+// (ep_slot; -1: none) of its region of the per-episode log in lane order (ballot
+// prefix); the lowest finishing lane publishes the count.  ep_base: the count before.
+struct EpLogClaim {
+  const EnvParams& P;
+  int lane;
+  uint32_t ep_base;
+  int64_t& ep_slot;
+  __device__ void operator()(const StepOut& so) const {
+    if (!P.ep_rows) return;
+    const uint64_t m = __ballot(so.done);
+    if (m == 0) return;
+    const int lid = threadIdx.x & 63;
+    if (so.done) {
+      const uint32_t at = ep_base + (uint32_t)__popcll(m & ((1ull << lid) - 1ull));
+      if (at < (uint32_t)P.ep_cap) ep_slot = (int64_t)(lane >> 6) * P.ep_cap + at;
+    }
+    if (lid == __ffsll((unsigned long long)m) - 1) P.ep_cnt[lane >> 6] = ep_base + (uint32_t)__popcll(m);
+  }
+};
+
+// env_step_lane's risk writer: the claimed row's risk columns
+struct EpLogRisk {
+  const EnvParams& P;
+  const int64_t& ep_slot;
+  __device__ void operator()(int k, double v) const {
+    if (ep_slot >= 0 && k < P.ep_w - 4) P.ep_rows[ep_slot * P.ep_w + 4 + k] = (float)v;
+  }
+};
+
+// the claimed row's header [step, lane, final reward, length]
+__device__ __forceinline__ void ep_log_header(const EnvParams& P, int64_t ep_slot, uint32_t step, int lane,
+                                              const StepOut& o, int t) {
+  if (ep_slot >= 0) {
+    float* er = P.ep_rows + ep_slot * P.ep_w;
+    er[0] = (float)step;
+    er[1] = (float)lane;
+    er[2] = (float)o.reward;
+    er[3] = (float)t;
+  }
+}
+
+__device__ __forceinline__ void replay_row_scalars(const rlmd::ReplayView& rb, int lane, int64_t row, const StepOut& o) {
+  rb.reward[row] = (float)o.reward;  // max(reward, r_abs_zero = -inf)
+  rb.done[row] = o.learn_done;
+  if (rb.n_steps > 1) rlmd::ms_record(rb, lane, row, o.learn_done);
+}
+
+// a finished lane counts its episode and resets (obs: its reset state); a live one commits wealth and time
+template <int FAM>
+__device__ __forceinline__ void lane_reset_or_commit(const EnvParams& P, int lane, const StepOut& o, int t, uint32_t ep,
+                                                     float* obs, double& st_n, double& st_r, double& st_t) {
+  if (o.done) {
+    st_n = 1.0;
+    st_r = o.reward;
+    st_t = (double)t;
+    env_reset_lane<FAM>(P, lane, [&](int k, double v) { obs[(int64_t)lane * P.state_dim + k] = (float)v; }, -1, ep);
+  } else {
+    P.wealth[lane] = o.W;
+    P.time[lane] = t + 1;
+  }
+}
+
+// episode statistics: both kernels write the same rows, one per 64 lanes (plain stores: atomics on
+// one address from every wave serialise across the XCDs).  A wave's sums, in a fixed order:
+__device__ __forceinline__ void wave_stats_sum(double& st_n, double& st_r, double& st_t) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    st_n += __shfl_xor(st_n, m, 64);
+    st_r += __shfl_xor(st_r, m, 64);
+    st_t += __shfl_xor(st_t, m, 64);
+  }
+}
+
+// act_env_kernel's row (every thread of the block calls; its 64 lanes sit in wave 0)
+__device__ __forceinline__ void block_stats_out(const StatFold& sf, double st_n, double st_r, double st_t) {
+  if (sf.part_out) {
+    __shared__ double red[3][256 / 64];
+    wave_stats_sum(st_n, st_r, st_t);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+      red[0][w] = st_n;
+      red[1][w] = st_r;
+      red[2][w] = st_t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      const int q = threadIdx.x;
+      double v = 0.0;
+      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v += red[q][i];
+      sf.part_out[(int64_t)blockIdx.x * 4 + q] = v;
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------
 // fused training step: action (warm-up draw | policy) -> action_window clip ->
@@ -576,7 +272,7 @@ __global__ void __launch_bounds__(256) env_train_kernel(EnvParams P, uint32_t st
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   RLMD_TSE(0, __builtin_amdgcn_s_memrealtime());
   RLMD_TSE(1, __builtin_amdgcn_s_memtime());
-  // block 0 folds the previous launch's per-block rows into the caller's
+  // block 0 folds the previous launch's per-64-lane rows into the caller's
   // accumulator first (its rows are complete: that launch has ended)
   if (blockIdx.x == 0 && sf.fold_src) {
     __shared__ double fr[3][256];
@@ -606,8 +302,7 @@ __global__ void __launch_bounds__(256) env_train_kernel(EnvParams P, uint32_t st
         v = -kMaxAbsAction + 2.0 * kMaxAbsAction * u;
         if (abs_actions) v = fabs(v);
       }
-      if (sizeof(AT) == 4) return (AT)v;  // policy action outside the window: exact f32
-      return (AT)fmin(fmax(v, clip_lo), clip_hi);
+      return window_action<AT>(v, clip_lo, clip_hi);
     };
     // the actions in named registers when their count is known at compile time (an
     // array here was promoted to LDS, each element's load waited on at its store)
@@ -659,75 +354,23 @@ __global__ void __launch_bounds__(256) env_train_kernel(EnvParams P, uint32_t st
           if (alias) rb.state[row * S + k] = f;
           obs[(int64_t)lane * S + k] = f;
         },
-        [&](int k, double v) {
-          if (ep_slot >= 0 && k < P.ep_w - 4) P.ep_rows[ep_slot * P.ep_w + 4 + k] = (float)v;
-        },
-        [&](const StepOut& so) {
-          // finished lanes of this wave take consecutive rows of its region in lane
-          // order (ballot prefix); the lowest finishing lane publishes the count
-          if (!P.ep_rows) return;
-          const uint64_t m = __ballot(so.done);
-          if (m == 0) return;
-          const int lid = threadIdx.x & 63;
-          if (so.done) {
-            const uint32_t at = ep_base + (uint32_t)__popcll(m & ((1ull << lid) - 1ull));
-            if (at < (uint32_t)P.ep_cap) ep_slot = (int64_t)(lane >> 6) * P.ep_cap + at;
-          }
-          if (lid == __ffsll((unsigned long long)m) - 1) P.ep_cnt[lane >> 6] = ep_base + (uint32_t)__popcll(m);
-        });
+        EpLogRisk{P, ep_slot}, EpLogClaim{P, lane, ep_base, ep_slot});
     RLMD_TSE(3, __builtin_amdgcn_s_memtime());
-    if (ep_slot >= 0) {
-      float* er = P.ep_rows + ep_slot * P.ep_w;
-      er[0] = (float)step;
-      er[1] = (float)lane;
-      er[2] = (float)o.reward;
-      er[3] = (float)t;
-    }
+    ep_log_header(P, ep_slot, step, lane, o, t);
     if (!alias) {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         if (j < S) rb.state[row * S + j] = s0[j];
     }
     for (int i = 0; i < A; ++i) rb.action[row * A + i] = (float)act(i);
-    rb.reward[row] = (float)o.reward;  // max(reward, r_abs_zero = -inf)
-    rb.done[row] = o.learn_done;
-    if (rb.n_steps > 1) rlmd::ms_record(rb, lane, row, o.learn_done);
-    if (o.done) {
-      st_n = 1.0;
-      st_r = o.reward;
-      st_t = (double)t;
-      env_reset_lane<FAM>(P, lane, [&](int k, double v) { obs[(int64_t)lane * S + k] = (float)v; }, -1, ep);
-    } else {
-      P.wealth[lane] = o.W;
-      P.time[lane] = t + 1;
-    }
+    replay_row_scalars(rb, lane, row, o);
+    lane_reset_or_commit<FAM>(P, lane, o, t, ep, obs, st_n, st_r, st_t);
     RLMD_TSE(4, __builtin_amdgcn_s_memtime());
   }
-  // episode statistics: a fixed-order block reduction into this block's row of
-  // the launch's partial buffer (plain stores; device-scope atomics on one
-  // address from every wave serialise across the XCDs and cost more than the
-  // whole env step)
-  if (sf.part_out) {
-    __shared__ double red[3][256 / 64];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-      st_n += __shfl_xor(st_n, m, 64);
-      st_r += __shfl_xor(st_r, m, 64);
-      st_t += __shfl_xor(st_t, m, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-      red[0][w] = st_n;
-      red[1][w] = st_r;
-      red[2][w] = st_t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      const int q = threadIdx.x;
-      double v = 0.0;
-      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v += red[q][i];
-      sf.part_out[(int64_t)blockIdx.x * 4 + q] = v;
-    }
+  if (sf.part_out && (lane & ~63) < P.n_lanes) {  // a wave that holds lanes: its row
+    wave_stats_sum(st_n, st_r, st_t);
+    double* row = sf.part_out + (int64_t)(lane >> 6) * 4;
+    if ((lane & 63) == 0) row[0] = st_n, row[1] = st_r, row[2] = st_t;
   }
   RLMD_TSE(5, __builtin_amdgcn_s_memtime());
   RLMD_TSE(6, __builtin_amdgcn_s_memrealtime());
@@ -864,27 +507,8 @@ __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA 
             obs[(int64_t)b * S + k] = f;
           }
         },
-        [&](int k, double v) {
-          if (ep_slot >= 0 && k < P.ep_w - 4) P.ep_rows[ep_slot * P.ep_w + 4 + k] = (float)v;
-        },
-        [&](const StepOut& so) {
-          if (!P.ep_rows) return;
-          const uint64_t m = __ballot(so.done);
-          if (m == 0) return;
-          const int lid = threadIdx.x & 63;
-          if (so.done) {
-            const uint32_t at = ep_base + (uint32_t)__popcll(m & ((1ull << lid) - 1ull));
-            if (at < (uint32_t)P.ep_cap) ep_slot = (int64_t)(b >> 6) * P.ep_cap + at;
-          }
-          if (lid == __ffsll((unsigned long long)m) - 1) P.ep_cnt[b >> 6] = ep_base + (uint32_t)__popcll(m);
-        });
-    if (ep_slot >= 0) {
-      float* er = P.ep_rows + ep_slot * P.ep_w;
-      er[0] = (float)step;
-      er[1] = (float)b;
-      er[2] = (float)o.reward;
-      er[3] = (float)t;
-    }
+        EpLogRisk{P, ep_slot}, EpLogClaim{P, b, ep_base, ep_slot});
+    ep_log_header(P, ep_slot, step, b, o, t);
     if constexpr (SR > 0) {
       float s0[SR];
 #pragma unroll
@@ -899,42 +523,11 @@ __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA 
       *reinterpret_cast<f32x2u*>(rb.action + row * 2) = f32x2u{act(0), act(1)};
     else
       for (int i = 0; i < A; ++i) rb.action[row * A + i] = act(i);
-    rb.reward[row] = (float)o.reward;
-    rb.done[row] = o.learn_done;
-    if (rb.n_steps > 1) rlmd::ms_record(rb, b, row, o.learn_done);
-    if (o.done) {
-      st_n = 1.0;
-      st_r = o.reward;
-      st_t = (double)t;
-      env_reset_lane<FAM>(P, b, [&](int k, double v) { obs[(int64_t)b * S + k] = (float)v; }, -1, ep);
-    } else {
-      P.wealth[b] = o.W;
-      P.time[b] = t + 1;
-    }
+    replay_row_scalars(rb, b, row, o);
+    lane_reset_or_commit<FAM>(P, b, o, t, ep, obs, st_n, st_r, st_t);
   };
   rlmd::actrows::act_rows<H1P, NB, SP, MA, PARK>(a, smem, pro, epi, park);
-  if (sf.part_out) {  // the block's finished-episode statistics, as env_train_kernel
-    __shared__ double red[3][256 / 64];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-      st_n += __shfl_xor(st_n, m, 64);
-      st_r += __shfl_xor(st_r, m, 64);
-      st_t += __shfl_xor(st_t, m, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-      red[0][w] = st_n;
-      red[1][w] = st_r;
-      red[2][w] = st_t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      const int q = threadIdx.x;
-      double v = 0.0;
-      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v += red[q][i];
-      sf.part_out[(int64_t)blockIdx.x * 4 + q] = v;
-    }
-  }
+  block_stats_out(sf, st_n, st_r, st_t);
 }
 
 // ---------------------------------------------------------------------------
@@ -953,11 +546,7 @@ __global__ void __launch_bounds__(256) eval_rollout_kernel(EnvParams P, uint32_t
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= P.n_lanes) return;
   const int A = P.action_dim, D = P.draw_dim, R = P.risk_dim;
-  auto act = [&](int i) -> AT {
-    const double v = (double)actions[(int64_t)lane * A + i];
-    if (sizeof(AT) == 4) return (AT)v;
-    return (AT)fmin(fmax(v, clip_lo), clip_hi);
-  };
+  auto act = [&](int i) -> AT { return window_action<AT>((double)actions[(int64_t)lane * A + i], clip_lo, clip_hi); };
   double w = P.wealth[lane];
   int t = P.time[lane];
   const int start = FAM == RLMD_MARKET ? P.start[lane] : 0;
@@ -1018,11 +607,7 @@ __global__ void __launch_bounds__(256) eval_market_step_kernel(EnvParams P, cons
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= P.n_lanes || !live[lane]) return;
   const int A = P.action_dim, S = P.state_dim, R = P.risk_dim;
-  auto act = [&](int i) -> AT {
-    const double v = (double)actions[(int64_t)lane * A + i];
-    if (sizeof(AT) == 4) return (AT)v;
-    return (AT)fmin(fmax(v, clip_lo), clip_hi);
-  };
+  auto act = [&](int i) -> AT { return window_action<AT>((double)actions[(int64_t)lane * A + i], clip_lo, clip_hi); };
   const double w0 = P.wealth[lane];
   const int t = P.time[lane];
   const int start = P.start[lane];
@@ -1245,11 +830,7 @@ __global__ void __launch_bounds__(256) eval_market_loop_kernel(rlmd::FusedActArg
           acts[jj] = tanhf(mu) * a.max_action;
         }
       }
-      auto act = [&](int i) -> AT {
-        const double v = (double)(i == 0 ? acts[0] : acts[1]);
-        if (sizeof(AT) == 4) return (AT)v;
-        return (AT)fmin(fmax(v, clip_lo), clip_hi);
-      };
+      auto act = [&](int i) -> AT { return window_action<AT>((double)(i == 0 ? acts[0] : acts[1]), clip_lo, clip_hi); };
       if (probe) RLMD_TSE(3, __builtin_amdgcn_s_memtime());
       const StepOut so = env_step_lane<RLMD_MARKET, NG, AT>(
           P, b, w, t, start, ep, act, [&](int) { return 0.0; },
@@ -1288,7 +869,6 @@ __global__ void __launch_bounds__(256) env_obs_reset_kernel(EnvParams P, float* 
   env_reset_lane<FAM>(P, lane, [&](int k, double v) { obs[(int64_t)lane * P.state_dim + k] = (float)v; });
 }
 
-// Host dispatch over the compile-time family (and n == 1) specialisations:
 // ---------------------------------------------------------------------------
 // per-episode log drain: exclusive scan of the waves' kept row counts (one
 // workgroup), then one 64-lane workgroup per wave copies its rows into the
@@ -1375,11 +955,10 @@ struct rlmd_env_s {
   uint32_t step_ctr = 0;
   double* d_prices = nullptr;
   // episode statistics of the fused train step (StatFold): two launches' worth
-  // of per-block rows, the parity of the next launch, and the accumulator the
+  // of per-64-lane rows, the parity of the next launch, and the accumulator the
   // last launch's rows still owe (nullptr when nothing is pending)
   double* d_part = nullptr;
-  int part_rows = 0, part_parity = 0;  // part_rows: per-parity capacity (64-lane blocks)
-  int pend_rows = 0;                   // rows the pending launch wrote
+  int part_rows = 0, part_parity = 0;  // part_rows: rows of a launch, one per 64 lanes
   double* pending_dst = nullptr;
   // per-episode log (EnvParams::ep_rows / ep_cnt) and the drain's scratch
   int64_t* ep_offs = nullptr;
@@ -1417,15 +996,32 @@ int env_dims_for(const rlmd_env_cfg& c, int& S, int& A, int& R, int& D) {
   return 1;
 }
 
-void env_train_launch_params(rlmd_env_t env, EnvParams*& P);
-
 int flush_stats(rlmd_env_t env, hipStream_t stream) {
   if (!env->pending_dst) return 0;
   const double* rows = env->d_part + (size_t)(env->part_parity ^ 1) * env->part_rows * 4;
-  hipLaunchKernelGGL(stat_fold_kernel, dim3(1), dim3(256), 0, stream, rows, env->pend_rows, env->pending_dst);
+  hipLaunchKernelGGL(stat_fold_kernel, dim3(1), dim3(256), 0, stream, rows, env->part_rows, env->pending_dst);
   RLMD_LAUNCH_CHECK();
   env->pending_dst = nullptr;
   return 0;
+}
+
+// The StatFold of one training launch: the pending launch's rows are settled now when they owe
+// another accumulator, else handed to this launch's block 0; its own rows go to the current parity.
+static int stat_fold_begin(rlmd_env_t env, double* ep_stats, hipStream_t stream, StatFold* sf) {
+  *sf = StatFold{nullptr, nullptr, nullptr, env->part_rows};
+  if (ep_stats) sf->part_out = env->d_part + (size_t)env->part_parity * env->part_rows * 4;
+  if (env->pending_dst != ep_stats) return flush_stats(env, stream);  // (nothing pending: no launch)
+  if (env->pending_dst) {
+    sf->fold_src = env->d_part + (size_t)(env->part_parity ^ 1) * env->part_rows * 4;
+    sf->fold_dst = env->pending_dst;
+  }
+  return 0;
+}
+
+// after the launch: its rows, one per 64 lanes, are pending for ep_stats
+static void stat_fold_end(rlmd_env_t env, double* ep_stats) {
+  env->pending_dst = ep_stats;
+  if (ep_stats) env->part_parity ^= 1;
 }
 
 int env_train(rlmd_env_t env, const rlmd::ReplayView& rb, int64_t ring_base, uint32_t step,
@@ -1435,16 +1031,8 @@ int env_train(rlmd_env_t env, const rlmd::ReplayView& rb, int64_t ring_base, uin
   const int N = env->P.n_lanes;
   const dim3 grid((N + 255) / 256), block(256);
   const bool f64 = window || random_actions;
-  StatFold sf{nullptr, nullptr, nullptr, env->pend_rows};
-  double* const last_rows = env->d_part + (size_t)(env->part_parity ^ 1) * env->part_rows * 4;
-  if (env->pending_dst && env->pending_dst != ep_stats) {  // different accumulator: settle it now
-    const int r = flush_stats(env, stream);
-    if (r) return r;
-  } else if (env->pending_dst) {
-    sf.fold_src = last_rows;
-    sf.fold_dst = env->pending_dst;
-  }
-  if (ep_stats) sf.part_out = env->d_part + (size_t)env->part_parity * env->part_rows * 4;
+  StatFold sf;
+  if (const int r = stat_fold_begin(env, ep_stats, stream, &sf)) return r;
   // hipExtLaunchKernelGGL: the optional events are stamped at this dispatch's begin / end
 #define TRAIN(F, NG)                                                                                          \
   {                                                                                                           \
@@ -1460,13 +1048,12 @@ int env_train(rlmd_env_t env, const rlmd::ReplayView& rb, int64_t ring_base, uin
   RLMD_ENV_DISPATCH(env->P, TRAIN);
 #undef TRAIN
   RLMD_LAUNCH_CHECK();
-  env->pending_dst = ep_stats;
-  if (ep_stats) {
-    env->part_parity ^= 1;
-    env->pend_rows = (int)grid.x;
-  }
+  stat_fold_end(env, ep_stats);
   return 0;
 }
+
+// the shapes of the NG = 1 instantiations: one gamble / asset, market: one observed day
+static bool one_gamble_one_day(const EnvParams& P) { return P.n == 1 && (P.fam != RLMD_MARKET || P.obs_days == 1); }
 
 // the fused instantiations: one gamble / asset (market: one observed day), S <= 8,
 // A <= 2; the env handle's switch (rlmd_train_set_fused; RLMD_NO_FUSED_ENV=1 at
@@ -1478,7 +1065,7 @@ bool env_act_fusable(rlmd_env_t env) {
   // and Dx state widths above 8 take the 16-pitch market instantiation
   if (env->fuse != 1 || P.action_dim > actrows::kMaxA4 || P.state_dim > 16) return false;
   // 3-4 actions (investors C, Dice_SH B / C): the one-gamble / one-day shapes
-  const bool ng1 = P.n == 1 && (P.fam != RLMD_MARKET || P.obs_days == 1);
+  const bool ng1 = one_gamble_one_day(P);
   if (P.action_dim > actrows::kMaxA && !(ng1 && P.state_dim <= 8)) return false;
   return P.state_dim <= 8 || P.fam == RLMD_MARKET;
 }
@@ -1495,20 +1082,12 @@ int env_act_train(rlmd_env_t env, const ReplayView& rb, int64_t ring_base, uint3
   if (!env_act_fusable(env) || !shape || a.n != P.n_lanes) return 0;
   const int N = P.n_lanes;
   const dim3 grid((N + actrows::kRows - 1) / actrows::kRows), block(256);
-  StatFold sf{nullptr, nullptr, nullptr, env->pend_rows};
-  double* const last_rows = env->d_part + (size_t)(env->part_parity ^ 1) * env->part_rows * 4;
-  if (env->pending_dst && env->pending_dst != ep_stats) {
-    const int r = flush_stats(env, stream);
-    if (r) return r;
-  } else if (env->pending_dst) {
-    sf.fold_src = last_rows;
-    sf.fold_dst = env->pending_dst;
-  }
-  if (ep_stats) sf.part_out = env->d_part + (size_t)env->part_parity * env->part_rows * 4;
+  StatFold sf;
+  if (const int r = stat_fold_begin(env, ep_stats, stream, &sf)) return r;
   // NG = 1: one gamble / asset, one observation day (the BASELINE configs); NG = 0:
   // n and the observation window read at run time (n_gambles / assets <= 2 with
   // A <= 2, market Dx at the 16-float staging pitch)
-  const bool ng1 = P.n == 1 && (P.fam != RLMD_MARKET || P.obs_days == 1);
+  const bool ng1 = one_gamble_one_day(P);
   RLMD_CHECK(ng1 || P.fam != RLMD_DICE_SH, "fused acting + env step: dice_sh has one die");
   RLMD_CHECK(sp == 8 || P.fam == RLMD_MARKET, "fused acting + env step: state wider than 8 (market only)");
   const bool wpc4 = actrows::act_wpc(h1p, P.action_dim > actrows::kMaxA ? actrows::kMaxA4 : actrows::kMaxA, grid.x) == 4;
@@ -1566,11 +1145,7 @@ int env_act_train(rlmd_env_t env, const ReplayView& rb, int64_t ring_base, uint3
 #undef FUSEDM
 #undef FUSEDW
   RLMD_LAUNCH_CHECK();
-  env->pending_dst = ep_stats;
-  if (ep_stats) {
-    env->part_parity ^= 1;
-    env->pend_rows = (int)grid.x;
-  }
+  stat_fold_end(env, ep_stats);
   *launched = true;
   return 0;
 }
@@ -1711,7 +1286,7 @@ int rlmd_env_create(const rlmd_env_cfg* cfg, const double* prices_host, int64_t 
   RLMD_HIP(hipMalloc(&P.time, sizeof(int32_t) * N));
   RLMD_HIP(hipMalloc(&P.start, sizeof(int32_t) * N));
   RLMD_HIP(hipMalloc(&P.episode, sizeof(uint32_t) * N));
-  e->part_rows = (int)((N + 63) / 64);  // the fused kernel's 64-lane blocks; 256-lane launches use fewer
+  e->part_rows = (int)((N + 63) / 64);
   RLMD_HIP(hipMalloc(&e->d_part, sizeof(double) * 8 * e->part_rows));
   RLMD_HIP(hipMemset(P.episode, 0xff, sizeof(uint32_t) * N));  // first reset -> episode 0
   RLMD_HIP(hipMemset(P.start, 0, sizeof(int32_t) * N));

@@ -562,6 +562,52 @@ void adam_copies(rlmd_agent_s* ag, AdamArgs& ad, const NetOff& o, int slot0, int
   }
 }
 
+// The Adam (+ Polyak, + compute copies) arguments of learn_body's two steps at
+// learn_step_cntr = cntr.  The fused steps add adam_scalars' host-side factors;
+// launch_bwd_w_adam computes them itself.
+AdamArgs critic_adam_args(rlmd_agent_s* ag, int64_t cntr) {  // both critics: one contiguous range
+  const rlmd_agent_cfg& c = ag->cfg;
+  AdamArgs ad{};
+  ad.p = ag->params + ag->off_c[0];
+  ad.g = ag->grads + ag->off_c[0];
+  ad.m = ag->m + ag->off_c[0];
+  ad.v = ag->v + ag->off_c[0];
+  ad.target = ag->target + ag->off_c[0];
+  ad.n = 2 * ag->critic.size;
+  ad.lr = c.lr_critic;
+  ad.tau = c.tau;
+  ad.cnt = (int32_t)cntr;
+  ad.interval = 1;
+  ad.polyak_interval = c.target_critic_update;
+  ad.st = ag->st;
+  adam_copies(ag, ad, ag->critic, SLOT_C0, 2, true);
+  return ad;
+}
+
+AdamArgs actor_adam_args(rlmd_agent_s* ag, int64_t cntr, float* stats) {  // SAC: + the temperature
+  const rlmd_agent_cfg& c = ag->cfg;
+  const bool sac = c.algo == RLMD_SAC;
+  AdamArgs ad{};
+  ad.p = ag->params + ag->off_actor;
+  ad.g = ag->grads + ag->off_actor;
+  ad.m = ag->m + ag->off_actor;
+  ad.v = ag->v + ag->off_actor;
+  ad.target = sac ? nullptr : ag->target + ag->off_actor;
+  ad.n = ag->actor.size;
+  ad.lr = c.lr_actor;
+  ad.tau = c.tau;
+  ad.cnt = (int32_t)cntr;
+  ad.interval = c.actor_update_interval;
+  ad.polyak_interval = sac ? 0 : c.target_actor_update;
+  ad.st = ag->st;
+  ad.temp = sac ? 1 : 0;
+  ad.lr_temp = c.lr_temp;
+  ad.temp_interval = c.temp_update_interval;
+  ad.stats = stats;
+  adam_copies(ag, ad, ag->actor, SLOT_ACTOR, 1, !sac);
+  return ad;
+}
+
 // One learn() on the mini-batch already in ag->sc (s, r, s2, done, xsa).
 // eps_a / eps_b: injected noise (nullable).  stats: [16] device.
 // Launches (SAC, actor step): fwd rows | critic loss | critic bwd rows | critic
@@ -788,20 +834,7 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       cu.w3s[g] = S_.w3s[g];
     }
     cu.x = mb.xsa;
-    AdamArgs ad{};
-    ad.p = Pc[0];
-    ad.g = Gc[0];
-    ad.m = ag->m + ag->off_c[0];
-    ad.v = ag->v + ag->off_c[0];
-    ad.target = Tc[0];
-    ad.n = 2 * co.size;
-    ad.lr = c.lr_critic;
-    ad.tau = c.tau;
-    ad.cnt = (int32_t)cntr;
-    ad.interval = 1;
-    ad.polyak_interval = c.target_critic_update;
-    ad.st = ag->st;
-    adam_copies(ag, ad, co, SLOT_C0, 2, true);
+    AdamArgs ad = critic_adam_args(ag, cntr);
     adam_scalars(ad.lr, ad.cnt / ad.interval, ad.step_size, ad.bc2_sqrt);
     cu.adam = ad;
     cu.tj = critic_update_tj(d);
@@ -844,21 +877,7 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       add_bwd_w(gb, H2, H1, B, S_.dc2[g], H2, S_.c1[g], H1, Gc[g] + co.w2, Gc[g] + co.b2);
       add_bwd_w(gb, H1, X, B, S_.dc1[g], H1, mb.xsa, X, Gc[g] + co.w1, Gc[g] + co.b1);
     }
-    AdamArgs ad{};
-    ad.p = Pc[0];
-    ad.g = Gc[0];
-    ad.m = ag->m + ag->off_c[0];
-    ad.v = ag->v + ag->off_c[0];
-    ad.target = Tc[0];
-    ad.n = 2 * co.size;
-    ad.lr = c.lr_critic;
-    ad.tau = c.tau;
-    ad.cnt = (int32_t)cntr;
-    ad.interval = 1;
-    ad.polyak_interval = c.target_critic_update;
-    ad.st = ag->st;
-    adam_copies(ag, ad, co, SLOT_C0, 2, true);
-    RLMD_TRY(launch_bwd_w_adam(ag, gb, ad, st));
+    RLMD_TRY(launch_bwd_w_adam(ag, gb, critic_adam_args(ag, cntr), st));
   }
   // ---- actor (+ temperature) update every actor_update_interval
   if (!actor_step) return 0;
@@ -920,24 +939,7 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       au.k = c.topk;
       au.topk = c.actor_topk;
       au.target_entropy = -(float)A;
-      AdamArgs ad{};
-      ad.p = P + ag->off_actor;
-      ad.g = Ga;
-      ad.m = ag->m + ag->off_actor;
-      ad.v = ag->v + ag->off_actor;
-      ad.target = sac ? nullptr : T + ag->off_actor;
-      ad.n = ao.size;
-      ad.lr = c.lr_actor;
-      ad.tau = c.tau;
-      ad.cnt = (int32_t)cntr;
-      ad.interval = c.actor_update_interval;
-      ad.polyak_interval = sac ? 0 : c.target_actor_update;
-      ad.st = ag->st;
-      ad.temp = sac ? 1 : 0;
-      ad.lr_temp = c.lr_temp;
-      ad.temp_interval = c.temp_update_interval;
-      ad.stats = stats;
-      adam_copies(ag, ad, ao, SLOT_ACTOR, 1, !sac);
+      AdamArgs ad = actor_adam_args(ag, cntr, stats);
       adam_scalars(ad.lr, ad.cnt / ad.interval, ad.step_size, ad.bc2_sqrt);
       if (ad.temp && ad.cnt % ad.temp_interval == 0)
         adam_scalars(ad.lr_temp, ad.cnt / ad.temp_interval, ad.temp_step_size, ad.temp_bc2_sqrt);
@@ -1018,25 +1020,7 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
     if (sac) add_bwd_w(gb, A, H2, B, S_.gh + A, 2 * A, S_.h2, H2, Ga + ao.w4, Ga + ao.b4);
     add_bwd_w(gb, H2, H1, B, S_.dh2, H2, S_.h1, H1, Ga + ao.w2, Ga + ao.b2);
     add_bwd_w(gb, H1, S, B, S_.dh1, H1, mb.s, S, Ga + ao.w1, Ga + ao.b1);
-    AdamArgs ad{};
-    ad.p = P + ag->off_actor;
-    ad.g = Ga;
-    ad.m = ag->m + ag->off_actor;
-    ad.v = ag->v + ag->off_actor;
-    ad.target = sac ? nullptr : T + ag->off_actor;
-    ad.n = ao.size;
-    ad.lr = c.lr_actor;
-    ad.tau = c.tau;
-    ad.cnt = (int32_t)cntr;
-    ad.interval = c.actor_update_interval;
-    ad.polyak_interval = sac ? 0 : c.target_actor_update;
-    ad.st = ag->st;
-    ad.temp = sac ? 1 : 0;
-    ad.lr_temp = c.lr_temp;
-    ad.temp_interval = c.temp_update_interval;
-    ad.stats = stats;
-    adam_copies(ag, ad, ao, SLOT_ACTOR, 1, !sac);
-    RLMD_TRY(launch_bwd_w_adam(ag, gb, ad, st));
+    RLMD_TRY(launch_bwd_w_adam(ag, gb, actor_adam_args(ag, cntr, stats), st));
   }
   return 0;
 }

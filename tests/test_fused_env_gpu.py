@@ -21,9 +21,9 @@ run-time n keep the two-launch path (acting kernel + env_train_kernel); the test
 asserts which path ran (rlmd_train_last_fused) and checks both.
 
 Fused vs unfused: the same seeded loop with rlmd_train_set_fused(1) and (0),
-learning on (K = 1), must produce bit-identical rings, wealth and parameters
-(act.hip and the fused kernel share rlmd_act_rows.h and both compile with FP
-contraction off).
+learning on (K = 1), must produce bit-identical rings, wealth, parameters,
+episode-log rows and episode statistics (act.hip and the fused kernel share
+rlmd_act_rows.h and both compile with FP contraction off).
 """
 import numpy as np
 import pytest
@@ -131,25 +131,35 @@ def _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days):
                                                 ("gbm", "C", 1, 1), ("coin", "C", 1, 1), ("dice_sh", "B", 1, 1),
                                                 ("dice_sh", "C", 1, 1), ("market", "C", 1, 1)])
 def test_fused_equals_unfused(golden, dev, env, inv, n, obs_days, algo):
+    """The statistics' f64 reward sums agree to the bit because both kernels write one
+    partial row per 64 lanes (env.hip wave_stats_sum) and one fold adds the rows."""
     N, T = 2048, 12
     out = []
     for fused in (1, 0):
         tr, _ = _trainer(dev, golden, env, inv, algo, N, T, k=1, seed=5, n=n, obs_days=obs_days)
         tr.set_fused(fused)  # per env handle
+        tr.episode_log(64)
         for t in range(T):
             tr.step()
             assert tr.last_fused() == bool(fused)
         ring = read_ring(tr, 0, N * T)
         w, tt = tr.env.lane_state()
-        out.append((ring, w, tt, tr.obs.cpu().numpy(), tr.agent.params.cpu().numpy().copy()))
+        out.append((ring, w, tt, tr.obs.cpu().numpy(), tr.agent.params.cpu().numpy().copy(), tr.drain_episodes(),
+                    tr.episode_stats()))
         del tr
-    (ra, wa, ta, oa, pa), (rb, wb, tb, ob, pb) = out
+    (ra, wa, ta, oa, pa, (ea, da), sa), (rb, wb, tb, ob, pb, (eb, db), sb) = out
     for name, x, y in zip(("s", "a", "r", "s2", "d"), ra, rb):
         np.testing.assert_array_equal(x, y, err_msg=f"ring {name}")
     np.testing.assert_array_equal(wa, wb)
     np.testing.assert_array_equal(ta, tb)
     np.testing.assert_array_equal(oa, ob)
     np.testing.assert_array_equal(pa, pb)  # the K = 1 updates learned from identical rings
+    # the two kernels share one epilogue (env.hip): the same episode log and statistics
+    np.testing.assert_array_equal(ea, eb, err_msg="episode log rows")
+    assert da == db, "episode log rows dropped"
+    if env == "market":
+        assert sa["episodes"] > 0 and len(ea) + da > 0  # 12-day episodes end inside the 12 steps
+    assert sa == sb, "episode statistics"
 
 
 @pytest.mark.parametrize("algo", ["SAC", "TD3"])
