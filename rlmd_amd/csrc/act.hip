@@ -30,11 +30,8 @@ namespace actrows {
 __device__ unsigned long long g_ts_act[4096][8];
 }  // namespace actrows
 }  // namespace rlmd
-#define RLMD_TSA(i, v)                                                                          \
-  do {                                                                                          \
-    if (threadIdx.x == 0 && blockIdx.x < 4096) ::rlmd::actrows::g_ts_act[blockIdx.x][i] = (v);  \
-  } while (0)
 #endif
+#define RLMD_TSA(i, v) RLMD_STAMP(threadIdx.x == 0 && blockIdx.x < 4096, ::rlmd::actrows::g_ts_act[blockIdx.x][i], v)
 
 #include "rlmd_act_rows.h"
 

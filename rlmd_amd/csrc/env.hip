@@ -20,14 +20,13 @@
 // stamps per workgroup — [0] / [6] realtime entry / exit, [1..5] cycles after each
 // phase, [7] realtime at the start of the per-row sampling + env epilogue
 __device__ unsigned long long g_ts_actenv[4096][8];
-#define RLMD_TSA(i, v)                                                                    \
-  do {                                                                                    \
-    if (threadIdx.x == 0 && blockIdx.x < 4096) {                                          \
-      g_ts_actenv[blockIdx.x][i] = (v);                                                   \
-      if ((i) == 5) g_ts_actenv[blockIdx.x][7] = __builtin_amdgcn_s_memrealtime();        \
-    }                                                                                     \
-  } while (0)
 #endif
+#define RLMD_TSA(i, v)                                                                        \
+  do {                                                                                        \
+    RLMD_STAMP(threadIdx.x == 0 && blockIdx.x < 4096, g_ts_actenv[blockIdx.x][i], v);         \
+    RLMD_STAMP(threadIdx.x == 0 && blockIdx.x < 4096 && (i) == 5, g_ts_actenv[blockIdx.x][7], \
+               __builtin_amdgcn_s_memrealtime());                                             \
+  } while (0)
 #include "rlmd_act_rows.h"
 #include "rlmd_common.h"
 #include "rlmd_internal.h"
@@ -40,15 +39,8 @@ namespace {
 // entry / exit of env_train_kernel and act_env_kernel, and thread 0's s_memtime
 // phase stamps of block 0
 __device__ unsigned long long g_ts_env[2048][8];
-#define RLMD_TSE(i, v)                                                                  \
-  do {                                                                                  \
-    if (threadIdx.x == 0 && blockIdx.x < 2048) g_ts_env[blockIdx.x][i] = (v);           \
-  } while (0)
-#else
-#define RLMD_TSE(i, v) \
-  do {                 \
-  } while (0)
 #endif
+#define RLMD_TSE(i, v) RLMD_STAMP(threadIdx.x == 0 && blockIdx.x < 2048, g_ts_env[blockIdx.x][i], v)
 
 // Finished-episode statistics of the fused train step: each launch writes one
 // row {episodes, sum of final rewards, sum of lengths, -} per 64 lanes into
@@ -421,9 +413,6 @@ struct ActEnvKargs {
   StatFold sf;
 };
 
-#ifndef RLMD_ACT_PARK
-#define RLMD_ACT_PARK 1  // act_env_kernel: the lane state and draw parked in LDS across the acting body
-#endif
 template <int FAM, int NG, int H1P, int NB, int SP, int MA, int WPC>
 __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA ? WPC : 2) : 1) act_env_kernel(rlmd::FusedActArgs a, EnvParams P, uint32_t step,
                                                       float* obs, rlmd::ReplayView rb, int64_t ring_base,
@@ -454,7 +443,7 @@ __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA 
     }
   };
   // the lane state and draw through LDS (rlmd_act_rows.h park()): [word][64 rows]
-  constexpr bool PARK = RLMD_ACT_PARK && rlmd::actrows::act_park(H1P, SP, MA, WPC);
+  constexpr bool PARK = rlmd::actrows::act_park(H1P, SP, MA, WPC);
   constexpr rlmd::actrows::ActLds LYP = rlmd::actrows::act_lds(H1P, SP, MA, PARK);
   uint32_t* pk = reinterpret_cast<uint32_t*>(smem + LYP.total);
   constexpr int kR = rlmd::actrows::kRows;
@@ -1093,8 +1082,8 @@ int env_act_train(rlmd_env_t env, const ReplayView& rb, int64_t ring_base, uint3
   const bool wpc4 = actrows::act_wpc(h1p, P.action_dim > actrows::kMaxA ? actrows::kMaxA4 : actrows::kMaxA, grid.x) == 4;
 #define FUSEDW(F, NG, H, B, SP, MA, W)                                                                                  \
   hipExtLaunchKernelGGL((act_env_kernel<F, NG, H, B, SP, MA, W>), grid, block,                                        \
-                        actrows::act_lds_bytes(H, SP, MA, RLMD_ACT_PARK && actrows::act_park(H, SP, MA, W)) +               \
-                            (RLMD_ACT_PARK && actrows::act_park(H, SP, MA, W) ? actrows::kParkBytes : 0), stream,            \
+                        actrows::act_lds_bytes(H, SP, MA, actrows::act_park(H, SP, MA, W)) +                            \
+                            (actrows::act_park(H, SP, MA, W) ? actrows::kParkBytes : 0), stream,                         \
                         ev_start, ev_stop, 0, a, env->P, step, obs, rb, ring_base, sf)
 #define FUSEDM(F, NG, H, B, SP, MA)                                                           \
   do {                                                                                        \

@@ -16,8 +16,12 @@
 // weight gradient of both critics) share a launch through blockIdx.x.
 #include "rlmd_common.h"
 #include "rlmd_gemm.h"
+#include "rlmd_mfma.h"
 
 namespace {
+
+using rlmd::bf16x8;
+using rlmd::f32x4;
 
 // Tile configurations (TM x TM outputs per 256-thread block, BK-deep K steps):
 //   TM = 64, BK = 64  for large M (acting over all lanes): 4 waves x 32x32
@@ -25,9 +29,6 @@ namespace {
 //                     128-deep K chunk per load round trip, 4x more blocks
 constexpr int PAD_F32 = 2;  // f32 rows of BK+2 words: 16 rows x 4 k columns spread over banks
 constexpr int PAD_BF = 8;   // bf16 rows of BK+8: 16-B aligned fragment reads
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned short f2bf(float f) {
   // round-to-nearest-even (finite inputs; NaN kept NaN)

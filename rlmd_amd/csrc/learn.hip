@@ -112,15 +112,8 @@ __global__ void __launch_bounds__(256) actor_head_kernel(HeadArgs h) {
 #ifdef RLMD_TIMING
 // experiment builds only (tools/ts_probe.py): thread-0 s_memtime checkpoints
 __device__ unsigned long long g_ts[64];
-#define RLMD_TS(i)                                                   \
-  do {                                                               \
-    if (threadIdx.x == 0) g_ts[i] = __builtin_amdgcn_s_memtime();    \
-  } while (0)
-#else
-#define RLMD_TS(i) \
-  do {             \
-  } while (0)
 #endif
+#define RLMD_TS(i) RLMD_STAMP(threadIdx.x == 0, g_ts[i], __builtin_amdgcn_s_memtime())
 
 template <int NTH>
 __global__ void __launch_bounds__(NTH) critic_loss_kernel(LossArgs a) {
@@ -240,7 +233,7 @@ struct Scratch {
   float *h1, *h2, *logp, *xsan, *save;
   float *e1[2], *e2[2], *qnpart[2], *dqn[2], *dlogp;
   float *gh, *dh2, *dh1;
-  // ReLU masks (bytes, rows.hip m1_index / m2_index layouts) of c1/c2, e1/e2, h1/h2
+  // ReLU masks (bytes, rows.hip m1_index / learn_kernels.h rp_index layouts) of c1/c2, e1/e2, h1/h2
   uint8_t *cm1[2], *cm2[2], *em1[2], *em2[2], *am1, *am2;
   float* stats;  // [16] when the caller passes none
   // fused critic update (update.hip): row-packed h1 / h2 (compute type), the

@@ -107,6 +107,19 @@ __host__ __device__ inline int64_t frag_index(int row, int col, int ld, int bf16
   return ((int64_t)((row >> 4) * (ld / KS) + s) * 64 + lane) * EPF + kin % EPF;
 }
 
+// Row-packed layout [B / 16][Hp][16] of what the forward row kernels (rows.hip)
+// hand to the weight-gradient tiles (update.hip): element (row, col) of a
+// [B x Hp] matrix at ((row / 16) * Hp + col) * 16 + row % 16.  The 8 (bf16) or 4
+// (f32) consecutive mini-batch rows an MFMA fragment lane holds along K are one
+// contiguous 16-byte run, and so are a column's 16 rows of a block.  h1, h2, the
+// backward bases (elements) and the [h2 > 0] masks (bytes) all use it.
+// A row kernel's workgroup is one 16-row block: it names the block and a row of
+// it (only the row's low 4 bits count); the tiles name the mini-batch row.
+__host__ __device__ inline int64_t rp_index(int rb, int Hp, int row, int col) {
+  return (((int64_t)rb * Hp + col) << 4) + (row & 15);
+}
+__host__ __device__ inline int64_t rp_index(int row, int Hp, int col) { return rp_index(row >> 4, Hp, row, col); }
+
 // A net as the row kernels see it: f32 master parameters plus compute copies of
 // fc2.weight in the MFMA operand type (bf16 or f32), zero-padded to 32:
 //   wc [H2p][H1p] (= fc2.weight, forward), wt [H1p][H2p] (transposed, backward).
@@ -145,7 +158,7 @@ struct FwdRowsArgs {
   const float* xsa;
   float* c1[2];
   float* c2[2];
-  uint8_t* cm1[2];  // ReLU masks of c1 / c2 in the backward layouts (rows.hip m1_index / m2_index)
+  uint8_t* cm1[2];  // ReLU masks of c1 / c2 in the backward layouts (rows.hip m1_index / rp_index)
   uint8_t* cm2[2];
   float* q[2];
   int32_t with_actor, a_mode, a_tag;

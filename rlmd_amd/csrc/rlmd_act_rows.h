@@ -9,6 +9,7 @@
 
 #include "learn_kernels.h"
 #include "rlmd_common.h"
+#include "rlmd_mfma.h"
 #include "rlmd_policy.h"
 
 #ifndef RLMD_TSA
@@ -20,8 +21,8 @@
 namespace rlmd {
 namespace actrows {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+using rlmd::bf16x8;  // members here too: env.hip reaches them through `using namespace actrows`
+using rlmd::f32x4;
 
 constexpr int kRows = 64;
 
@@ -311,12 +312,10 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
     bf16x8 bcur[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) bcur[nb] = bnext[nb];
-#if !defined(RLMD_ABL_ACT)
     if (k0 + 32 < H1P) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) bnext[nb] = wf[(nb * nS + k0 / 32 + 1) * 64];
     }
-#endif  // timing ablation (experiment builds only; results wrong): layer 2 without its fragment stream
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const bf16x8 af = *reinterpret_cast<const bf16x8*>(&h1s[(16 * m + (lane & 15)) * HP + k0 + kq]);

@@ -232,16 +232,7 @@ __device__ __forceinline__ void rlmd_kernarg_prefetch() {
   static_assert(BYTES >= 4, "kernel arguments below one dword");
   rlmd_karg_lines<n4, ((BYTES - 4) / 4) * 4>::run((const void*)__builtin_amdgcn_kernarg_segment_ptr());
 }
-#ifndef RLMD_KARG_PF
-#define RLMD_KARG_PF 1
-#endif
-#if RLMD_KARG_PF
 #define RLMD_KERNARG_PREFETCH(args) rlmd_kernarg_prefetch<(int)sizeof(args)>()
-#else
-#define RLMD_KERNARG_PREFETCH(args) \
-  do {                              \
-  } while (0)
-#endif
 
 // Write-through stores for data the next kernel reads (optimiser state, compute
 // copies, row-packed activations, bases): a device-scope store (sc1) sends each
@@ -249,21 +240,10 @@ __device__ __forceinline__ void rlmd_kernarg_prefetch() {
 // L2 for the release at the end of the kernel, which writes every dirty line
 // back after the last workgroup has finished (≈1 µs per MB at the update
 // kernels' sizes, on the critical path of every launch).
-#ifndef RLMD_WT_STORES
-#define RLMD_WT_STORES 1
-#endif
-#if RLMD_WT_STORES
 #define RLMD_WT_AUX 16  // buffer-store cache policy: sc1 (device scope)
-#else
-#define RLMD_WT_AUX 0
-#endif
 template <class T>
 __device__ __forceinline__ void rlmd_st_wt(T* p, T v) {
-#if RLMD_WT_STORES
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = v;
-#endif
 }
 // 16 bytes (16-byte aligned) as two 8-byte device-scope stores
 __device__ __forceinline__ void rlmd_st_wt16(void* p, float a, float b, float c, float d) {
@@ -271,6 +251,20 @@ __device__ __forceinline__ void rlmd_st_wt16(void* p, float a, float b, float c,
   rlmd_st_wt(q, (uint64_t)__float_as_uint(a) | ((uint64_t)__float_as_uint(b) << 32));
   rlmd_st_wt(q + 1, (uint64_t)__float_as_uint(c) | ((uint64_t)__float_as_uint(d) << 32));
 }
+
+// A timing stamp of the experiment builds (-DRLMD_TIMING, tools/ts_probe.py):
+// `lvalue = value` where cond holds; nothing at all in the production build.
+// Each kernel file wraps it in a macro that names its own array and clock.
+#ifdef RLMD_TIMING
+#define RLMD_STAMP(cond, lvalue, value) \
+  do {                                  \
+    if (cond) (lvalue) = (value);       \
+  } while (0)
+#else
+#define RLMD_STAMP(cond, lvalue, value) \
+  do {                                  \
+  } while (0)
+#endif
 
 __device__ inline uint64_t rlmd_block_bitonic(uint64_t key, int n, uint64_t* lds) {
   const int i = threadIdx.x;

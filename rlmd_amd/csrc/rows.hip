@@ -24,50 +24,30 @@
 #include "rlmd_loss.h"
 #include "rlmd_policy.h"
 #include "rlmd_common.h"
+#include "rlmd_mfma.h"
 
 namespace rlmd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int R = kRowBlock;  // rows per workgroup
 constexpr int NT = 512;       // threads per workgroup
 constexpr int NW = NT / 64;   // waves
 constexpr int NHF = 4;        // heads reduced in the MFMA epilogue (more -> LDS dot products)
 constexpr int W1P = 8;        // fc1 inputs preloaded per thread (more -> read in the loop)
 constexpr int kHeadsMax = 2 * RLMD_MAX_ACTION;
-#ifndef RLMD_FWD_DEFER
-#define RLMD_FWD_DEFER 1  // fwd_rows: a job's second fragment stream issued after its first net's layer 2
-#endif
-#ifndef RLMD_L1_BATCH
-#define RLMD_L1_BATCH 1  // row kernels' layer 1: a batch of rows' inputs read from LDS together
-#endif
-#ifndef RLMD_SAMPLE_NL
-#define RLMD_SAMPLE_NL 1  // fwd_rows: load-free policy sampling on the production path (sample_rows<true>)
-#endif
 
 #ifdef RLMD_TIMING
 // experiment builds only (tools/ts_probe.py): thread-0 s_memtime checkpoints of
 // workgroup (0, y) — slots [16 y, 16 y + 16) for fwd jobs, 96.. for abwd
 __device__ unsigned long long g_ts_rows[128];
-#define RLMD_TSR(i)                                                                      \
-  do {                                                                                   \
-    if (threadIdx.x == 0 && blockIdx.x == 0) g_ts_rows[i] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-// job windows (constant-rate clock, comparable across workgroups): block x = 0
-#define RLMD_TSJ(i)                                                                          \
-  do {                                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x == 0) g_ts_rows[i] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define RLMD_TSJ(i) \
-  do {              \
-  } while (0)
-#define RLMD_TSR(i) \
-  do {              \
-  } while (0)
 #endif
+#define RLMD_TSR(i) RLMD_STAMP(threadIdx.x == 0 && blockIdx.x == 0, g_ts_rows[i], __builtin_amdgcn_s_memtime())
+// job windows (constant-rate clock, comparable across workgroups): block x = 0
+#define RLMD_TSJ(i) RLMD_STAMP(threadIdx.x == 0 && blockIdx.x == 0, g_ts_rows[i], __builtin_amdgcn_s_memrealtime())
 
+// f32 -> bf16 in integer arithmetic: round to nearest even, a NaN keeps its high
+// payload bits with the quiet bit set.  Not update.hip's bf16_rne (the hardware
+// convert): other instructions and another NaN payload, so the two stay apart.
 __device__ __forceinline__ unsigned short to_bf16(float f) {
   unsigned u = __float_as_uint(f);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
@@ -75,31 +55,12 @@ __device__ __forceinline__ unsigned short to_bf16(float f) {
   return (unsigned short)(u >> 16);
 }
 
+// the row kernels' precision trait: the shared MFMA step and the operand convert
 template <int PREC>
-struct CT;
-template <>
-struct CT<RLMD_BF16> {
-  using T = unsigned short;
-  using Frag = bf16x8;
-  static constexpr int KS = 32;  // k covered by one 16-byte fragment per lane
-  __device__ __forceinline__ static T cvt(float f) { return to_bf16(f); }
-  __device__ __forceinline__ static void mfma(const Frag& a, const Frag& b, f32x4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct CT<RLMD_FP32> {
-  using T = float;
-  using Frag = f32x4;
-  static constexpr int KS = 16;
-  __device__ __forceinline__ static T cvt(float f) { return f; }
-  // lane group q = lane >> 4 holds k = k0 + 4q + j in element j: four 16x16x4
-  // MFMAs cover k0 .. k0 + 15 (a permutation of the k order, same products)
-  __device__ __forceinline__ static void mfma(const Frag& a, const Frag& b, f32x4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+struct CT : Mfma<PREC> {
+  __device__ __forceinline__ static typename Mfma<PREC>::T cvt(float f) {
+    if constexpr (PREC == RLMD_BF16) return to_bf16(f);
+    else return f;
   }
 };
 
@@ -327,20 +288,11 @@ __device__ __forceinline__ void fwd_const(FwdConst<NBW>& k, const float* p, cons
 //   m1 [row block][band][lane][4]: the MFMA accumulator layout over H1p (dh1) —
 //      a lane's 4 rows of one column are one 4-byte word;
 //   m2 [row block][column][16 rows]: the elementwise map over H2p (dh2) — a
-//      thread's kMR consecutive rows are kMR contiguous bytes.
+//      thread's kMR consecutive rows are kMR contiguous bytes.  This is the
+//      row-packed layout of the weight-gradient tiles' operands (rp_index,
+//      learn_kernels.h), in bytes.
 __device__ __forceinline__ int64_t m1_index(int rb, int H1p, int row, int col) {
   return ((((int64_t)rb * (H1p >> 4) + (col >> 4)) * 64 + (col & 15) + 16 * ((row & 15) >> 2)) << 2) + (row & 3);
-}
-__device__ __forceinline__ int64_t m2_index(int rb, int H2p, int row, int col) {
-  return (((int64_t)rb * H2p + col) << 4) + (row & 15);
-}
-
-// Row-packed operands of the weight-gradient tiles (update.hip): element (b, c)
-// of a [B x Hp] matrix at ((b / 16) * Hp + c) * 16 + b % 16, so the 8 (bf16) or
-// 4 (f32) consecutive mini-batch rows an MFMA fragment lane holds along K are
-// one contiguous 16-byte run.
-__device__ __forceinline__ int64_t rp_index(int rb, int Hp, int row, int col) {
-  return (((int64_t)rb * Hp + col) << 4) + (row & 15);
 }
 
 // Extra outputs of one net's forward for the fused update kernels (nullable
@@ -418,7 +370,7 @@ __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, c
       mk[0] |= bit;
     }
   };
-  if (RLMD_L1_BATCH && in <= W1P && (ldx & 3) == 0) {
+  if (in <= W1P && (ldx & 3) == 0) {
     // every input in registers (k.w1, zero past in): a batch of rows' xs as 16-byte
     // LDS reads issued together, then their dots (j ascending, as below).  The
     // per-row loop waited one LDS round trip per row, its bounds being run-time.
@@ -524,7 +476,7 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBW], const FwdC
 #pragma unroll
         for (int h = 0; h < NHF; ++h) ph[rg][h] = fmaf(v, k.hw[i][h], ph[rg][h]);
       }
-      if (m2_out) rlmd_st_wt(reinterpret_cast<uint32_t*>(m2_out + m2_index(row0 / R, pad32(H2), acc_row(0), col)), mw);
+      if (m2_out) rlmd_st_wt(reinterpret_cast<uint32_t*>(m2_out + rp_index(row0 / R, pad32(H2), acc_row(0), col)), mw);
       // the lane's 4 rows of h2, contiguous in the row-packed layout
       if (ex && ex->hp2) store_rp_rows<PREC, 4>(ex->hp2, rp_index(row0 / R, pad32(H2), acc_row(0), col), hz, 4);
     }
@@ -907,28 +859,23 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     Pre<PREC, NBW, MULTI> pa, pc;
     pre_issue<PREC, NBW, MULTI>(pa, an.wc, H1p, H1p, H2p / 16);
     // the target critic's constants and fc2 stream: issued after the policy's
-    // layer 2 (RLMD_FWD_DEFER; 0: with this first round)
+    // layer 2 (with this first round they queued behind the policy's and delayed it)
     auto issue_critic = [&] {
       critic_const<NBW>(kc, cn, a.co, d, nb0);
       pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
     };
-    if constexpr (!RLMD_FWD_DEFER) issue_critic();
     if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 0, L.ldx, row0, B);
     const Noise2 nz = pre_nz ? noise_pre(smp, d, a.t_tag, row0) : Noise2{{0.f, 0.f}};
     RLMD_TSR(16 * job + 1);
     stage_commit(sr, s2, d.S, xs, L.ldx, row0, B);
     __syncthreads();
     RLMD_TSR(16 * job + 2);
-    if constexpr (RLMD_FWD_DEFER)
-      mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
-                                 d.A, smem, L, nullptr, nullptr, row0, B, nullptr, nullptr, nullptr, 0, 0, issue_critic,
-                                 6);
-    else
-      mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
-                                 d.A, smem, L, nullptr, nullptr, row0, B);
+    mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
+                               d.A, smem, L, nullptr, nullptr, row0, B, nullptr, nullptr, nullptr, 0, 0, issue_critic,
+                               6);
     RLMD_TSR(16 * job + 3);
     // load-free sampling on the production path (no injected noise): see sample_rows
-    if (RLMD_SAMPLE_NL && pre_nz && d.A <= 2)
+    if (pre_nz && d.A <= 2)
       sample_rows<true>(an.p, a.ao, d, smp, xs, L.ldx, hout, 0, a.t_tag, nullptr, a.t_noise_std, a.t_noise_clip,
                         a.t_clamp, job == 0 && !nxt && p == 0 ? a.logp_next : nullptr, nullptr, nullptr, row0, B, hb,
                         true, nz, true);
@@ -962,7 +909,6 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     auto issue_basis = [&] {
       if (upd) pre_issue<PREC, NBW, MULTI>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0);
     };
-    if constexpr (!RLMD_FWD_DEFER) issue_basis();
     stage_commit(sr, a.xsa, d.X, xs, L.ldx, row0, B);
     __syncthreads();
     if (job == 2) RLMD_TSR(61);
@@ -975,12 +921,8 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
       uint8_t* m1s = reinterpret_cast<uint8_t*>(smem + L.m1s);
       // h1 is the same in both halves: half 0 writes it
       const FwdExtra<PREC> ex{p == 0 ? static_cast<T*>(a.hp1[g]) : nullptr, static_cast<T*>(a.hp2[g]), m1s, aU};
-      if constexpr (RLMD_FWD_DEFER)
-        mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                                   nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw, issue_basis);
-      else
-        mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                                   nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw);
+      mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
+                                 nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw, issue_basis);
       // the backward basis of these rows: U1 = [h1 > 0] * (([h2 > 0] w3) W2), so
       // that the critic update forms dh1 = dq * U1 once dq is known (update.hip);
       // a half's partial U1 over its fc2 columns
@@ -1022,7 +964,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
                                d.A, smem, L, fa ? nullptr : a.h1a, fa ? nullptr : a.h2a, row0, B, a.am1, a.am2, &ex);
     RLMD_TSR(82);
-    if (RLMD_SAMPLE_NL && (pre_nz || a.a_mode == 1) && a.eps_cur == nullptr && d.A <= 2)
+    if ((pre_nz || a.a_mode == 1) && a.eps_cur == nullptr && d.A <= 2)
       sample_rows<true>(an.p, a.ao, d, a.smp, xs, L.ldx, hout, a.a_mode, a.a_tag, nullptr, 0.f, 0.f, 0, a.logp, a.save,
                         a.xsan, row0, B, hb, true, nz, true);
     else
@@ -1060,7 +1002,7 @@ __device__ __forceinline__ void bwd_mask(BwdMask<NBW>& k, const uint8_t* m1, con
   uint32_t wd[NWD + 1];
 #pragma unroll
   for (int w = 0; w <= NWD; ++w) {
-    const int64_t e = m2_index(rb, H2p, rbase + 4 * w, m.c);
+    const int64_t e = rp_index(rb, H2p, rbase + 4 * w, m.c);
     const bool need = m.r0 < R && (w < NWD || sh != 0);
     wd[w] = __builtin_amdgcn_raw_buffer_load_b32(r2, need ? (int)e : 0x7fffffff, 0, 0);
   }
@@ -1152,7 +1094,6 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
   // the basis pass's stream: after the forward's layer 2 (as fwd_rows' critic jobs)
   auto issue_basis = [&] { pre_issue<PREC, NBW, MULTI>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0); };
   if (upd) {
-    if constexpr (!RLMD_FWD_DEFER) issue_basis();
     const __amdgpu_buffer_rsrc_t rp = rlmd_rsrc(cn.p, a.co.size * 4);
 #pragma unroll
     for (int i = 0; i < NBW; ++i) {
@@ -1176,12 +1117,8 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     const uint8_t* m1s = reinterpret_cast<const uint8_t*>(smem + L.m1s);
     float* part = reinterpret_cast<float*>(smem + L.part);
     const FwdExtra<PREC> ex{nullptr, nullptr, reinterpret_cast<uint8_t*>(smem + L.m1s), aU};
-    if constexpr (RLMD_FWD_DEFER)
-      mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                                 nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw, issue_basis);
-    else
-      mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                                 nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw);
+    mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
+                               nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw, issue_basis);
     f32x4 acc[NBW];
     mfma_rows<PREC, NBW, MULTI>(pw, aU, L.lda1, cn.wt, H2p, ke, H1p / 16, acc, 0, ks0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -28,93 +28,57 @@
 #include "rlmd_adam.h"
 #include "rlmd_block.h"
 #include "rlmd_loss.h"
+#include "rlmd_mfma.h"
 #include "rlmd_policy.h"
 #include "rlmd_update.h"
 
 namespace rlmd {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int NT = 512;
-#ifndef RLMD_W1_HALF
-#define RLMD_W1_HALF 1  // the actor step's fc1 blocks 16 units wide (0: 32): twice the blocks, half the bases each
-#endif
-constexpr int TW = 32;
+constexpr int TW = 32;  // tile edge (fc2.weight tiles TW x TW, the critic step's fc1 blocks of TW rows)
 // the actor step's fc1 block width: its bases (nh x B x TW1 f32) made it the
-// launch's last workgroup to finish at 32 (128 KB of loads at C2)
-constexpr int TW1 = RLMD_W1_HALF ? 16 : 32;
+// launch's last workgroup to finish at 32 (128 KB of loads at C2); at 16 there
+// are twice the blocks with half the bases each
+constexpr int TW1 = 16;
 constexpr int kW1G = NT / TW1;      // row groups of an fc1 block (a thread per unit and group)
 constexpr int kW1R = 512 / kW1G;    // rows per group (B <= 512)
 constexpr int kW1Q = kW1R / 4;      // f32x4 base loads per thread and head
-// timing ablations (experiment builds only, RLMD_EXTRA_FLAGS=-DRLMD_ABL=<bits>; the
-// results are wrong): 1 no ranking (rank = row), 2 no optimiser step / copies
-#ifndef RLMD_ABL
-#define RLMD_ABL 0
-#endif
-#ifndef RLMD_ROLE_SPLIT
-#define RLMD_ROLE_SPLIT 1  // role-specialised update bodies (0: one body, roles' loads predicated off)
-#endif
-#ifndef RLMD_SPLIT_SPEC
-#define RLMD_SPLIT_SPEC 1  // critic step bodies specialised on fwd_rows' column split (0: one body, halves predicated)
-#endif
-#ifndef RLMD_W1_EARLY
-#define RLMD_W1_EARLY 1  // the actor step's fc1 block loads its operands before the ranking (0: after)
-#endif
-template <int NW>
-__device__ __forceinline__ void upd_rank(uint64_t key, uint64_t* runs, int* out) {
-  if constexpr ((RLMD_ABL & 1) != 0) {
-    out[threadIdx.x] = (int)threadIdx.x;
-    __syncthreads();
-  } else {
-    block_rank<NW>(key, runs, out);
-  }
-}  // tile edge (fc2.weight tiles TW x TW, fc1 blocks of TW rows)
 
 #ifdef RLMD_TIMING
-// experiment builds only (tools/ts_probe.py upd): thread-0 s_memtime stamps of
-// three workgroups (slot 0: tile (0, 0), 1: tile (0, 1), 2: the first fc1 block)
+// experiment builds only (tools/ts_probe.py upd): thread-0 stamps of six
+// workgroups (ts_slot in the bodies), 16 per workgroup
 __device__ unsigned long long g_ts_upd[128];
 __device__ unsigned long long g_ts_aupd[128];
+#endif
 #ifdef RLMD_TIMING_WINDOWS  // entry / exit windows only: the phase stamps perturb the register allocation
 #define RLMD_TS_ON(i) ((i) >= 14)
 #else
 #define RLMD_TS_ON(i) true
 #endif
 // RLMD_TIMING_DRAIN: the exit stamp waits until the workgroup's stores have completed
-#ifdef RLMD_TIMING_DRAIN
-#define RLMD_TS_DRAIN(i)                              \
-  if ((i) == 15) {                                    \
+#if defined(RLMD_TIMING) && defined(RLMD_TIMING_DRAIN)
+#define RLMD_TS_DRAIN(i)                                 \
+  if ((i) == 15) {                                       \
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
-    __syncthreads();                                  \
+    __syncthreads();                                     \
   }
 #else
 #define RLMD_TS_DRAIN(i)
 #endif
-#define RLMD_TSU(i)                                                                       \
-  do {                                                                                    \
-    RLMD_TS_DRAIN(i)                                                                      \
-    if (RLMD_TS_ON(i) && threadIdx.x == 0 && ts_slot >= 0)                                \
-      g_ts_upd[ts_slot * 16 + (i)] = (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
-  } while (0)
-// actor step: cycles (i < 14) and the constant-rate clock (i = 14, 15: entry / exit)
-#define RLMD_TSA(i)                                                                        \
+// cycles (i < 14) and the constant-rate clock (i = 14, 15: entry / exit)
+#define RLMD_TS_AT(arr, i)                                                                 \
   do {                                                                                     \
     RLMD_TS_DRAIN(i)                                                                       \
-    if (RLMD_TS_ON(i) && threadIdx.x == 0 && ts_slot >= 0)                                 \
-      g_ts_aupd[ts_slot * 16 + (i)] = (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
+    RLMD_STAMP(RLMD_TS_ON(i) && threadIdx.x == 0 && ts_slot >= 0, arr[ts_slot * 16 + (i)], \
+               (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime()); \
   } while (0)
-#else
-#define RLMD_TSU(i) \
-  do {              \
-  } while (0)
-#define RLMD_TSA(i) \
-  do {              \
-  } while (0)
-#endif
+#define RLMD_TSU(i) RLMD_TS_AT(g_ts_upd, i)   // critic step
+#define RLMD_TSA(i) RLMD_TS_AT(g_ts_aupd, i)  // actor step
 
 // f32 -> bf16, round to nearest even: the plain cast lowers to v_cvt_pk_bf16_f32
-// (NaN stays NaN; no per-element branch)
+// (NaN stays NaN; no per-element branch).  Not rows.hip's to_bf16 (integer
+// rounding): other instructions and another NaN payload, so the two stay apart.
 __device__ __forceinline__ unsigned short bf16_rne(float f) {
   return __builtin_bit_cast(unsigned short, (__bf16)f);
 }
@@ -162,14 +126,8 @@ __device__ __forceinline__ void tile_copies(const float* pcl, const CopyDst& cd,
 template <int PREC>
 struct KT;
 template <>
-struct KT<RLMD_BF16> {
+struct KT<RLMD_BF16> : Mfma<RLMD_BF16> {  // KS: rows per K-step
   static constexpr int RPL = 8;   // consecutive rows per lane
-  static constexpr int KS = 32;   // rows per K-step
-  using T = unsigned short;
-  using Frag = bf16x8;
-  __device__ __forceinline__ static void mfma(const Frag& a, const Frag& b, f32x4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
   __device__ __forceinline__ static Frag load_b(__amdgpu_buffer_rsrc_t r, int64_t elem, bool ok) {
     return __builtin_bit_cast(Frag, __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (int)(elem * 2) : 0x7fffffff, 0, 0));
   }
@@ -191,17 +149,8 @@ struct KT<RLMD_BF16> {
   }
 };
 template <>
-struct KT<RLMD_FP32> {
+struct KT<RLMD_FP32> : Mfma<RLMD_FP32> {
   static constexpr int RPL = 4;
-  static constexpr int KS = 16;
-  using T = float;
-  using Frag = f32x4;
-  __device__ __forceinline__ static void mfma(const Frag& a, const Frag& b, f32x4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-  }
   __device__ __forceinline__ static Frag load_b(__amdgpu_buffer_rsrc_t r, int64_t elem, bool ok) {
     return __builtin_bit_cast(Frag, __builtin_amdgcn_raw_buffer_load_b128(r, ok ? (int)(elem * 4) : 0x7fffffff, 0, 0));
   }
@@ -217,9 +166,42 @@ struct KT<RLMD_FP32> {
   }
 };
 
-__device__ __forceinline__ int64_t rp_idx(int row, int Hp, int col) {
-  return (((int64_t)(row >> 4) * Hp + col) << 4) + (row & 15);
-}
+// A head workgroup's prefetch of one h2 column and its mask over a thread's 32
+// rows (two 16-row blocks hb of the row-packed layout, 16 bytes of mask and 16
+// elements of h2 each).
+template <int PREC>
+struct H2Column {
+  using T = typename KT<PREC>::T;
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  static constexpr int NV = 16 * sizeof(T) / 16;  // 16-byte loads per 16 rows of h2
+  u32x4 fmb[2], fhv[2][NV];
+
+  // column i, rows [32 p, 32 p + 32); on = false: predicated off
+  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rm2, __amdgpu_buffer_rsrc_t rh2, int p, int i, int H2p,
+                                       int nrb, bool on) {
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      const int r0 = 32 * p + 16 * hb;
+      const bool ok = on && r0 < nrb * 16;
+      const int64_t ix = rp_index(r0, H2p, i);
+      fmb[hb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rm2, ok ? (int)ix : 0x7fffffff, 0, 0));
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        fhv[hb][v] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                   rh2, ok ? (int)(ix * sizeof(T) + 16 * v) : 0x7fffffff, 0, 0));
+    }
+  }
+  // row e of block hb: the mask byte and h2 as f32
+  __device__ __forceinline__ void at(int hb, int e, uint32_t& byte, float& h) const {
+    byte = (fmb[hb][e >> 2] >> (8 * (e & 3))) & 0xffu;
+    if constexpr (PREC == RLMD_BF16) {
+      const uint32_t w = fhv[hb][e >> 3][(e >> 1) & 3];
+      h = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
+    } else {
+      h = __uint_as_float(fhv[hb][e >> 2][e & 3]);
+    }
+  }
+};
 
 // LDS of the critic update (bytes)
 struct ULds {
@@ -272,17 +254,11 @@ __global__ void __launch_bounds__(NT) critic_update_kernel(CritUpdArgs a) {
     return;
   }
   const int g = blockIdx.x / per, t = blockIdx.x - g * per;
-#if RLMD_ROLE_SPLIT
   if (t < a.n_w2) critic_update_body<PREC, WIDE, kRoleW2, SPLIT>(a, smem, g, t);
   else if (t >= a.n_w2 + a.n_w1) critic_update_body<PREC, WIDE, kRoleHead, SPLIT>(a, smem, g, t);
   else critic_update_body<PREC, WIDE, kRoleW1, SPLIT>(a, smem, g, t);
-#else
-  critic_update_body<PREC, WIDE, -1, SPLIT>(a, smem, g, t);
-#endif
 }
 
-// ROLE -1: one body for every role, the roles' loads issued predicated-off (the
-// round-5 form, RLMD_ROLE_SPLIT=0)
 template <int PREC, bool WIDE, int ROLE, bool SPLIT>
 __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigned char* smem, int g, int t) {
   using K = KT<PREC>;
@@ -293,16 +269,12 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
   const int B = d.B, H1 = d.H1, H2 = d.H2, H1p = d.H1p, H2p = d.H2p, X = d.X;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrb = (B + 15) / 16;
-  // this workgroup's role; IS_* = the role's loads are compiled in
-  constexpr bool IS_W2 = ROLE < 0 || ROLE == kRoleW2, IS_W1 = ROLE < 0 || ROLE == kRoleW1,
-                 IS_HEAD = ROLE < 0 || ROLE == kRoleHead;
-  const bool w2tile = ROLE < 0 ? t < a.n_w2 : ROLE == kRoleW2;
-  const bool first_col = ROLE < 0 ? t >= a.n_w2 + a.n_w1 : ROLE == kRoleHead;  // first_col: a head workgroup
+  // this workgroup's role (first_col: a head workgroup)
+  constexpr bool w2tile = ROLE == kRoleW2, w1blk = ROLE == kRoleW1, first_col = ROLE == kRoleHead;
   constexpr int TJ = WIDE ? 2 * TW : TW;  // fc2.weight columns per tile
   constexpr int NH = WIDE ? 2 : 1;        // 32-column halves per tile
   const int i0 = w2tile ? (t / a.tj) * TW : first_col ? (t - a.n_w2 - a.n_w1) * TW : 0;
   const int j0 = w2tile ? (t % a.tj) * TJ : first_col ? 0 : (t - a.n_w2) * TW;
-  const bool w1blk = ROLE < 0 ? !w2tile && !first_col : ROLE == kRoleW1;
   const int wrow = WIDE ? (wave & 3) : wave;     // this wave's 64-row slice of the batch
   const int jw = j0 + (WIDE ? 32 * (wave >> 2) : 0);  // and its 32-column half
   const int64_t pbase = (int64_t)g * co.size;  // this critic's parameters in the Adam base
@@ -311,7 +283,7 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
   // Adam on an element of this critic (fc2.weight elements also refresh the copies)
   auto step = [&](int pi, float gv, const AdamIn& in) {
     const int j = pi - (int)pbase - (int)co.w2;
-    if (!(RLMD_ABL & 2)) adam_apply_dst(a.adam, pi, gv, in, polyak, (j >= 0 && j < H1 * H2) ? j : -1, cd);
+    adam_apply_dst(a.adam, pi, gv, in, polyak, (j >= 0 && j < H1 * H2) ? j : -1, cd);
   };
   const int bx = blockIdx.x, pb = a.n_w2 + a.n_w1 + a.ti;
   const int ts_slot = bx == 0 ? 0 : bx == 1 ? 1 : bx == a.n_w2 ? 2 : bx == a.n_w2 + a.n_w1 ? 3 : bx == pb ? 4
@@ -320,10 +292,11 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
   RLMD_TSU(14);
   RLMD_TSU(0);
 
-  // ---- first load round: loss inputs, this workgroup's operands, Adam state.
-  //      Branch-free: every load is issued by every workgroup, predicated through
-  //      the range check on its role (a load inside `if (role)` is copied out of
-  //      its registers at the merge, which waits for it on the spot)
+  // ---- first load round: loss inputs, this role's operands, Adam state.  The
+  //      role is a compile-time test, so only its own loads exist in this body;
+  //      inside the role nothing is loaded under a run-time branch (such a load is
+  //      copied out of its registers at the merge, which waits for it on the
+  //      spot): edges are predicated through the buffer range check instead
   const CriticLoads cl = critic_row_load<SPLIT>(a.loss);
   // (a) dW2 tile: per wave rows [64 w, 64 w + 64), per K-step the A masks (two i
   //     sub-blocks) and B fragments (two j sub-blocks)
@@ -333,60 +306,45 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
   const __amdgpu_buffer_rsrc_t rm2 = rlmd_rsrc(a.m2[g], (int64_t)nrb * H2p * 16),
                                rh1 = rlmd_rsrc(a.hp1[g], (int64_t)nrb * H1p * 16 * sizeof(typename K::T));
   float w3l[2];
-  if constexpr (IS_W2) {
+  if constexpr (w2tile) {
 #pragma unroll
   for (int s = 0; s < NKS; ++s) {
     const int row = 64 * wrow + s * K::KS + K::RPL * (lane >> 4);
-    const bool rok = w2tile && row < nrb * 16;
+    const bool rok = row < nrb * 16;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int i = i0 + 16 * h + (lane & 15), j = jw + 16 * h + (lane & 15);
-      K::load_mask(rm2, rp_idx(row, H2p, i), rok && i < H2p, mw[s][h]);
-      bf[s][h] = K::load_b(rh1, rp_idx(row, H1p, j), rok && j < H1p);
+      K::load_mask(rm2, rp_index(row, H2p, i), rok && i < H2p, mw[s][h]);
+      bf[s][h] = K::load_b(rh1, rp_index(row, H1p, j), rok && j < H1p);
     }
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int i = i0 + 16 * h + (lane & 15);
-    w3l[h] = rlmd_ldf(rlmd_rsrc(a.w3s[g], (int64_t)H2 * 4), i, w2tile && i < H2);
+    w3l[h] = rlmd_ldf(rlmd_rsrc(a.w3s[g], (int64_t)H2 * 4), i, i < H2);
   }
   }
   // (b) Adam state of the owned parameters: 1024 elements per 32-column half, 2
   //     per thread and half
   int pidx[NH][2];
   AdamIn ain[NH][2];
-  if constexpr (IS_W2) {
+  if constexpr (w2tile) {
 #pragma unroll
   for (int hf = 0; hf < NH; ++hf)
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int el = tid * 2 + e, blk = el >> 8, ln = (el >> 2) & 63, rg = el & 3;
       const int i = i0 + 16 * (blk >> 1) + 4 * (ln >> 4) + rg, j = j0 + 32 * hf + 16 * (blk & 1) + (ln & 15);
-      pidx[hf][e] = (w2tile && i < H2 && j < H1) ? (int)(pbase + co.w2 + (int64_t)i * H1 + j) : -1;
+      pidx[hf][e] = (i < H2 && j < H1) ? (int)(pbase + co.w2 + (int64_t)i * H1 + j) : -1;
       ain[hf][e] = adam_load(a.adam, pidx[hf][e], polyak);
     }
   }
-  // (c) first-column tiles: this thread's column of h2 and [h2 > 0] over its 32 rows
+  // (c) head workgroups: this thread's column of h2 and [h2 > 0] over its 32 rows
   //     (thread: column i0 + tid % 32, rows [32 p, 32 p + 32) of part p = tid / 32)
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  constexpr int NV = 16 * sizeof(typename K::T) / 16;  // 16-byte loads per 16 rows of h2
-  u32x4 fmb[2], fhv[2][NV];
-  if constexpr (IS_HEAD) {
-    const int ci = tid & 31, p = tid >> 5, i = i0 + ci;
-    const __amdgpu_buffer_rsrc_t rh2 = rlmd_rsrc(a.hp2[g], (int64_t)nrb * H2p * 16 * sizeof(typename K::T));
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      const int r0 = 32 * p + 16 * hb;
-      const bool ok = first_col && r0 < nrb * 16;
-      const int64_t ix = rp_idx(r0, H2p, i);
-      fmb[hb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rm2, ok ? (int)ix : 0x7fffffff, 0, 0));
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        fhv[hb][v] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rh2, ok ? (int)(ix * sizeof(typename K::T) + 16 * v) : 0x7fffffff,
-                                                   0, 0));
-    }
-  }
+  H2Column<PREC> hcol;
+  if constexpr (first_col)
+    hcol.load(rm2, rlmd_rsrc(a.hp2[g], (int64_t)nrb * H2p * 16 * sizeof(typename K::T)), tid >> 5, i0 + (tid & 31), H2p,
+              nrb, true);
   // (e) Adam state of the parameters stepped after the tile: on the first tile
   //     column b2 / w3 (threads 0..63) and b3 (thread 64 of tile 0), on an fc1
   //     block W1 / b1 (thread c * 32 + jj: input c < X, or c = 8 for the bias)
@@ -400,20 +358,20 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
       xpi = (int)(pbase + (ci == 8 ? co.b1 + jr : co.w1 + (int64_t)jr * X + ci));
   }
   AdamIn xin{};
-  if constexpr (IS_W1 || IS_HEAD) xin = adam_load(a.adam, xpi, polyak);
+  if constexpr (w1blk || first_col) xin = adam_load(a.adam, xpi, polyak);
   float w3c = 0.f;
-  if constexpr (IS_HEAD) w3c = rlmd_ldf(rlmd_rsrc(a.w3s[g], (int64_t)H2 * 4), i0 + (tid & 31), first_col && tid < 32);
+  if constexpr (first_col) w3c = rlmd_ldf(rlmd_rsrc(a.w3s[g], (int64_t)H2 * 4), i0 + (tid & 31), tid < 32);
   // (d) fc1 blocks: the critic inputs of this thread's 8 LDS slots and U1 of its
   //     column over its 32 rows
   float* xs = reinterpret_cast<float*>(smem + ULds::xs);
   float xv[8];
   f32x4 u1v[8], u1w[8];  // U1, and its second partial half (fwd_rows column split)
-  if constexpr (IS_W1) {
+  if constexpr (w1blk) {
     const __amdgpu_buffer_rsrc_t rx = rlmd_rsrc(a.x, (int64_t)B * X * 4);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int e = tid + q * NT, r = e >> 3, c = e & 7;
-      xv[q] = rlmd_ldf(rx, (int64_t)r * X + c, w1blk && r < B && c < X);
+      xv[q] = rlmd_ldf(rx, (int64_t)r * X + c, r < B && c < X);
     }
     const int cj = tid & 31, p = tid >> 5, j = j0 + cj;
     const bool us = SPLIT && a.loss.qsplit > 1;
@@ -422,12 +380,12 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int r = 32 * p + 4 * q;
-      const bool ok = w1blk && r < nrb * 16 && j < H1p;
+      const bool ok = r < nrb * 16 && j < H1p;
       u1v[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                             ru, ok ? (int)(rp_idx(r, H1p, j) * 4) : 0x7fffffff, 0, 0));
+                                             ru, ok ? (int)(rp_index(r, H1p, j) * 4) : 0x7fffffff, 0, 0));
       if constexpr (SPLIT)
         u1w[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                               ru, (ok && us) ? (int)((ustr + rp_idx(r, H1p, j)) * 4) : 0x7fffffff, 0, 0));
+                                               ru, (ok && us) ? (int)((ustr + rp_index(r, H1p, j)) * 4) : 0x7fffffff, 0, 0));
       else
         u1w[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -441,17 +399,13 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
     CriticRow o;
     // the block sums only where the loss itself needs them (CIM kernel, TCAU
     // truncation): the statistics workgroups form the rest (rlmd_loss.h)
-#ifndef RLMD_LOSS_BLOCK_ALWAYS
     critic_row_loss(a.loss, red, o, cl, critic_loss_needs_block(a.loss));
-#else
-    critic_row_loss(a.loss, red, o, cl);
-#endif
     RLMD_TSU(2);
     const int kk = B > a.loss.k ? a.loss.k : B;
     bool sel = o.in;
     if (B > a.loss.k) {
       int* rank_of = reinterpret_cast<int*>(smem + ULds::rank);
-      upd_rank<NT / 64>(critic_sel_key(o), reinterpret_cast<uint64_t*>(smem + ULds::runs), rank_of);
+      block_rank<NT / 64>(critic_sel_key(o), reinterpret_cast<uint64_t*>(smem + ULds::runs), rank_of);
       sel = o.in && rank_of[tid] < kk;
       if (blockIdx.x == 0 && a.rank_out && o.in) a.rank_out[tid] = rank_of[tid];  // for the statistics
     }
@@ -462,7 +416,7 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
   __syncthreads();
   RLMD_TSU(3);
 
-  if (IS_W2 && w2tile) {
+  if constexpr (w2tile) {
     // ---- dW2[i0.., j0..] = sum_b dh2[b, i] h1[b, j] over this wave's rows
     f32x4 acc[2][2];
 #pragma unroll
@@ -501,7 +455,7 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
 #pragma unroll
         for (int w = 0; w < 8 / NH; ++w) gs += part[(hf * (8 / NH) + w) * 1024 + el];
         float pn = 0.f, tn = 0.f;  // padding elements: zero in the copies
-        if (pidx[hf][e] >= 0 && !(RLMD_ABL & 2)) adam_core(a.adam, pidx[hf][e], gs, ain[hf][e], polyak, pn, tn);
+        if (pidx[hf][e] >= 0) adam_core(a.adam, pidx[hf][e], gs, ain[hf][e], polyak, pn, tn);
         float* ph = pcl + hf * 2 * 32 * 33;
         ph[ii * 33 + jj] = pn;
         ph[32 * 33 + ii * 33 + jj] = tn;
@@ -510,9 +464,9 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
 #pragma unroll
     for (int hf = 0; hf < NH; ++hf)
       if (j0 + 32 * hf < H1p)  // WIDE: the last tile's second half may lie past the padded width
-        if (!(RLMD_ABL & 2)) tile_copies<PREC>(pcl + hf * 2 * 32 * 33, cd, polyak && cd.twc, i0, j0 + 32 * hf, H1p, H2p);
+        tile_copies<PREC>(pcl + hf * 2 * 32 * 33, cd, polyak && cd.twc, i0, j0 + 32 * hf, H1p, H2p);
     RLMD_TSU(5);
-  } else if (IS_HEAD && first_col) {
+  } else if constexpr (first_col) {
     {
       // ---- db2[i] = w3[i] sum_b dq[b] [h2 > 0], dW3[i] = sum_b dq[b] h2[b, i]
       //      (thread: column i0 + tid % 32, rows [32 p, 32 p + 32) of part p = tid / 32)
@@ -524,14 +478,9 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const float q = dqs[r0 + e];
-          const uint32_t byte = (fmb[hb][e >> 2] >> (8 * (e & 3))) & 0xffu;
+          uint32_t byte;
           float h;
-          if constexpr (PREC == RLMD_BF16) {
-            const uint32_t w = fhv[hb][e >> 3][(e >> 1) & 3];
-            h = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-          } else {
-            h = __uint_as_float(fhv[hb][e >> 2][e & 3]);
-          }
+          hcol.at(hb, e, byte, h);
           sm += byte ? q : 0.f;
           sh = fmaf(q, h, sh);
         }
@@ -552,7 +501,7 @@ __device__ __forceinline__ void critic_update_body(const CritUpdArgs& a, unsigne
       }
       RLMD_TSU(6);
     }
-  } else if (IS_W1) {
+  } else {
     // ---- dW1[j, x] = sum_b dq[b] U1[b, j] x[b, x], db1[j] = sum_b dq[b] U1[b, j]
     //      (thread: fc1 row j0 + tid % 32, rows [32 p, 32 p + 32) of part p)
     const int cj = tid & 31, p = tid >> 5;
@@ -646,20 +595,17 @@ __global__ void __launch_bounds__(NT) actor_update_kernel(ActUpdArgs a) {
     replay_draw_role<NT>(a.draw, (int)(blockIdx.x - (gridDim.x - a.draw.n)), smem);
     return;
   }
-#if RLMD_ROLE_SPLIT
   if (t < a.n_w2) actor_update_body<PREC, kRoleW2>(a, smem);
   else if (t < a.n_w2 + a.n_w1) actor_update_body<PREC, kRoleW1>(a, smem);
   else actor_update_body<PREC, kRoleHead>(a, smem);  // heads and the statistics workgroups
-#else
-  actor_update_body<PREC, -1>(a, smem);
-#endif
 }
 
 template <int PREC, int ROLE>
 __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned char* smem) {
   using K = KT<PREC>;
-  constexpr bool IS_W2 = ROLE < 0 || ROLE == kRoleW2, IS_W1 = ROLE < 0 || ROLE == kRoleW1,
-                 IS_HEAD = ROLE < 0 || ROLE == kRoleHead;
+  // this workgroup's role; the head body also holds the statistics workgroups, so
+  // first_col (a head workgroup proper) is a run-time test inside it
+  constexpr bool w2tile = ROLE == kRoleW2, w1blk = ROLE == kRoleW1, head = ROLE == kRoleHead;
   float* ghs = reinterpret_cast<float*>(smem + ALds::gh);
   float* ghp = reinterpret_cast<float*>(smem + ALds::ghp);
   float* part = reinterpret_cast<float*>(smem + ALds::part);
@@ -672,7 +618,6 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nrb = (B + 15) / 16;
   const int t = blockIdx.x;
-  (void)IS_W1;
   // workgroups: fc2.weight tiles, fc1 blocks, head workgroups (b2 and the heads
   // of 32 fc2 rows each), and two critic-statistics workgroups.  Every reader of
   // log alpha and the Cauchy scales takes the update's starting slot, the
@@ -687,17 +632,15 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
   RLMD_TSA(14);
   RLMD_TSA(0);
   LearnState* st = a.st;
-  const bool stats_wg = IS_HEAD && sidx >= 0;
-  const bool w2tile = ROLE < 0 ? t < a.n_w2 : ROLE == kRoleW2;
-  const bool first_col = ROLE < 0 ? !stats_wg && t >= a.n_w2 + a.n_w1 : ROLE == kRoleHead && !stats_wg;  // a head workgroup
-  const bool w1blk = ROLE < 0 ? !stats_wg && !w2tile && !first_col : ROLE == kRoleW1;
+  const bool stats_wg = head && sidx >= 0;
+  const bool first_col = head && !stats_wg;
   const int i0 = w2tile ? (t / a.tj) * TW : first_col ? (t - a.n_w2 - a.n_w1) * TW : 0;
   const int j0 = w2tile ? (t % a.tj) * TW : w1blk ? (t - a.n_w2) * TW1 : 0;
   const bool polyak = adam_polyak(a.adam);
   const CopyDst cd = copy_dst(a.adam, 0);
   auto step = [&](int pi, float gv, const AdamIn& in) {
     const int j = pi - (int)ao.w2;
-    if (!(RLMD_ABL & 2)) adam_apply_dst(a.adam, pi, gv, in, polyak, (j >= 0 && j < H1 * H2) ? j : -1, cd);
+    adam_apply_dst(a.adam, pi, gv, in, polyak, (j >= 0 && j < H1 * H2) ? j : -1, cd);
   };
   float v = 0.f, lpv = 0.f, alpha = 0.f;
   bool sel = false;
@@ -727,9 +670,9 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
   }
   float* xs = reinterpret_cast<float*>(smem + ALds::xs);
   RLMD_TSA(1);
-  // ---- first load round, branch-free (predicated on the workgroup's role through
-  //      the range checks, as in critic_update_kernel): the row's loss inputs, the
-  //      tile operands, Adam state, the fc1 block's states and first two bases
+  // ---- first load round (this role's loads only, edges predicated through the
+  //      range checks, as in critic_update_body): the row's loss inputs, then the
+  //      tile operands and Adam state, or the fc1 block's states and first two bases
   const bool in = tid < B;
   const int64_t nB = (int64_t)B * 4;
   const int QP = a.qsplit > 1 ? 2 : 1;  // partial halves of q / dq/da / bases (qeval_rows column split)
@@ -763,16 +706,16 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
   const __amdgpu_buffer_rsrc_t rm2 = rlmd_rsrc(a.am2, (int64_t)nrb * H2p * 16),
                                rh1 = rlmd_rsrc(a.hp1a, (int64_t)nrb * H1p * 16 * sizeof(typename K::T));
   const __amdgpu_buffer_rsrc_t rw = rlmd_rsrc(a.wheads, (int64_t)nh * H2 * 4);
-  if constexpr (IS_W2) {
+  if constexpr (w2tile) {
 #pragma unroll
   for (int s = 0; s < NKS; ++s) {
     const int row = 64 * wave + s * K::KS + K::RPL * (lane >> 4);
-    const bool rok = w2tile && row < nrb * 16;
+    const bool rok = row < nrb * 16;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int i = i0 + 16 * h + (lane & 15), j = j0 + 16 * h + (lane & 15);
-      K::load_mask(rm2, rp_idx(row, H2p, i), rok && i < H2p, mw[s][h]);
-      bf[s][h] = K::load_b(rh1, rp_idx(row, H1p, j), rok && j < H1p);
+      K::load_mask(rm2, rp_index(row, H2p, i), rok && i < H2p, mw[s][h]);
+      bf[s][h] = K::load_b(rh1, rp_index(row, H1p, j), rok && j < H1p);
     }
   }
 #pragma unroll
@@ -781,20 +724,18 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
 #pragma unroll
     for (int q = 0; q < kHM; ++q) {  // summation order
       const int hq = head_at(q, A, sac);
-      wh[h][q] = rlmd_ldf(rw, (int64_t)(hq < 0 ? 0 : hq) * H2 + i, w2tile && hq >= 0 && i < H2);
+      wh[h][q] = rlmd_ldf(rw, (int64_t)(hq < 0 ? 0 : hq) * H2 + i, hq >= 0 && i < H2);
     }
   }
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int el = tid * 2 + e, blk = el >> 8, ln = (el >> 2) & 63, rg = el & 3;
     const int i = i0 + 16 * (blk >> 1) + 4 * (ln >> 4) + rg, j = j0 + 16 * (blk & 1) + (ln & 15);
-    pidx[e] = (w2tile && i < H2 && j < H1) ? (int)(ao.w2 + (int64_t)i * H1 + j) : -1;
+    pidx[e] = (i < H2 && j < H1) ? (int)(ao.w2 + (int64_t)i * H1 + j) : -1;
     ain[e] = adam_load(a.adam, pidx[e], polyak);
   }
   }
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  constexpr int NV = 16 * sizeof(typename K::T) / 16;  // 16-byte loads per 16 rows of h2
-  u32x4 fmb[2], fhv[2][NV];
+  H2Column<PREC> hcol;
   float whc[kHM];
   int xpi = -1;
   AdamIn xin;
@@ -810,7 +751,7 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int e = tid + q * NT, r = e >> 3, c = e & 7;
-      xv[q] = rlmd_ldf(rx, (int64_t)r * S + c, w1blk && r < B && c < S);
+      xv[q] = rlmd_ldf(rx, (int64_t)r * S + c, r < B && c < S);
     }
     const int j = j0 + tid % TW1, p = tid / TW1;
 #pragma unroll
@@ -818,21 +759,20 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
 #pragma unroll
       for (int q = 0; q < kW1Q; ++q) {
         const int r = kW1R * p + 4 * q;
-        const bool ok = w1blk && h < nh && r < nrb * 16 && j < H1p;
+        const bool ok = h < nh && r < nrb * 16 && j < H1p;
         uv[h][q] = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ru, ok ? (int)((h * ustride + rp_idx(r, H1p, j)) * 4) : 0x7fffffff,
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ru, ok ? (int)((h * ustride + rp_index(r, H1p, j)) * 4) : 0x7fffffff,
                                                          0, 0));
       }
   };
   auto w1_adam = [&]() {
     const int c = tid / TW1, jr = j0 + tid % TW1;
-    if (w1blk && tid < TW1 * 9 && (c < S || c == 8) && jr < H1)
+    if (tid < TW1 * 9 && (c < S || c == 8) && jr < H1)
       xpi = (int)(c == 8 ? ao.b1 + jr : ao.w1 + (int64_t)jr * S + c);
   };
-  // an fc1 block with its own body issues them with the first load round, under
-  // the loss and the ranking (the fc1 block is the actor step's last role to finish)
-  constexpr bool W1_EARLY = ROLE == kRoleW1 && RLMD_W1_EARLY;
-  if constexpr (W1_EARLY) {
+  // an fc1 block issues them with the first load round, under the loss and the
+  // ranking (the fc1 block is the actor step's last role to finish)
+  if constexpr (w1blk) {
     load_w1();
     w1_adam();
     xin = adam_load(a.adam, xpi, polyak);
@@ -849,32 +789,19 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
     sel = in;
     if (a.topk) {
       int* rank_of = reinterpret_cast<int*>(smem + ALds::rank);
-      upd_rank<NT / 64>(in ? ((uint64_t)(sac ? ~f2key(v) : f2key(v)) << 32) | (uint32_t)tid : ~0ull,
+      block_rank<NT / 64>(in ? ((uint64_t)(sac ? ~f2key(v) : f2key(v)) << 32) | (uint32_t)tid : ~0ull,
                  reinterpret_cast<uint64_t*>(smem + ALds::runs), rank_of);
       sel = in && rank_of[tid] < kk;
     }
     RLMD_TSA(2);
-    // without role bodies, after the ranking, to bound register use
-    if constexpr (IS_W1 && !W1_EARLY) load_w1();
     // the first tile column's operands: h2 / [h2 > 0] of its column over the
     // thread's 32 rows, the heads' weights, and the Adam state of b2 / the heads'
     // rows (thread c * 32 + ci: c = 0 b2, 1..nh head c - 1) and biases (thread
     // 288 + h); on an fc1 block the Adam state of W1 / b1 (thread c * 32 + jj)
-    if constexpr (IS_HEAD) {
-      const int ci = tid & 31, p = tid >> 5, i = i0 + ci;
-      const __amdgpu_buffer_rsrc_t rh2 = rlmd_rsrc(a.hp2a, (int64_t)nrb * H2p * 16 * sizeof(typename K::T));
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        const int r0 = 32 * p + 16 * hb;
-        const bool ok = first_col && r0 < nrb * 16;
-        const int64_t ix = rp_idx(r0, H2p, i);
-        fmb[hb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rm2, ok ? (int)ix : 0x7fffffff, 0, 0));
-#pragma unroll
-        for (int q = 0; q < NV; ++q)
-          fhv[hb][q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                     rh2, ok ? (int)(ix * sizeof(typename K::T) + 16 * q) : 0x7fffffff,
-                                                     0, 0));
-      }
+    if constexpr (head) {
+      const int i = i0 + (tid & 31);
+      hcol.load(rm2, rlmd_rsrc(a.hp2a, (int64_t)nrb * H2p * 16 * sizeof(typename K::T)), tid >> 5, i, H2p, nrb,
+                first_col);
 #pragma unroll
       for (int q = 0; q < kHM; ++q) {  // summation order
         const int hq = head_at(q, A, sac);
@@ -888,8 +815,7 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
                                                    : ao.w4 + (int64_t)(c - 1 - A) * H2 + ii);
       if (first_col && i0 == 0 && tid >= 288 && tid < 288 + nh)
         xpi = (int)(tid - 288 < A ? ao.b3 + (tid - 288) : ao.b4 + (tid - 288 - A));
-      if constexpr (IS_W1 && !W1_EARLY) w1_adam();
-      if constexpr ((IS_W1 && !W1_EARLY) || IS_HEAD) xin = adam_load(a.adam, xpi, polyak);
+      if constexpr (head) xin = adam_load(a.adam, xpi, polyak);
     }
     // ---- dL/da per row, then through the sampling and the heads (rlmd_policy.h)
     const float dv = sel ? -1.f / (float)kk : 0.f;
@@ -934,7 +860,7 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
   temperature_step();
   RLMD_TSA(4);
 
-  if (IS_W2 && w2tile) {
+  if constexpr (w2tile) {
     // ---- dW2 = sum_b dh2[b, i] h1[b, j], dh2 = [h2 > 0] (sum_h gh[b, h] W_head[h, i])
     f32x4 acc[2][2];
 #pragma unroll
@@ -976,14 +902,14 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
 #pragma unroll
       for (int w = 0; w < 8; ++w) gs += part[w * 1024 + el];
       float pn = 0.f, tn = 0.f;
-      if (pidx[e] >= 0 && !(RLMD_ABL & 2)) adam_core(a.adam, pidx[e], gs, ain[e], polyak, pn, tn);
+      if (pidx[e] >= 0) adam_core(a.adam, pidx[e], gs, ain[e], polyak, pn, tn);
       pcl[ii * 33 + jj] = pn;
       pcl[32 * 33 + ii * 33 + jj] = tn;
     }
     __syncthreads();
-    if (!(RLMD_ABL & 2)) tile_copies<PREC>(pcl, cd, polyak && cd.twc, i0, j0, H1p, H2p);
+    tile_copies<PREC>(pcl, cd, polyak && cd.twc, i0, j0, H1p, H2p);
     RLMD_TSA(6);
-  } else if (IS_HEAD && first_col) {
+  } else if (head && first_col) {
     {
       // ---- db2[i] = sum_b dh2[b, i]; the heads dW_head[h, i] = sum_b gh[b, h] h2[b, i]
       const int ci = tid & 31, p = tid >> 5;
@@ -993,19 +919,12 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {  // the part's two 16-row blocks of column i (prefetched)
         const int r0 = 32 * p + 16 * hb;
-        const u32x4& mb = fmb[hb];
-        const u32x4(&hv)[NV] = fhv[hb];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const float* gr = ghs + (r0 + e) * kHM;
-          const uint32_t byte = (mb[e >> 2] >> (8 * (e & 3))) & 0xffu;
+          uint32_t byte;
           float hval;
-          if constexpr (PREC == RLMD_BF16) {
-            const uint32_t w = hv[e >> 3][(e >> 1) & 3];
-            hval = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-          } else {
-            hval = __uint_as_float(hv[e >> 2][e & 3]);
-          }
+          hcol.at(hb, e, byte, hval);
           const float* grp = ghp + (r0 + e) * kHM;
           float acc_h = 0.f;
 #pragma unroll
@@ -1040,7 +959,7 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
         }
       }
     }
-  } else if (IS_W1) {
+  } else {
     // ---- dW1[j, x] = sum_b dh1[b, j] s[b, x], db1[j]; dh1 = sum_h gh[b, h] U_h[b, j]
     const int cj = tid % TW1, p = tid / TW1, j = j0 + cj;
 #pragma unroll
@@ -1064,7 +983,7 @@ __device__ __forceinline__ void actor_update_body(const ActUpdArgs& a, unsigned 
         const int r = kW1R * p + 4 * q;
         const bool ok = r < nrb * 16 && j < H1p;
         u[q] = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ru, ok ? (int)((h * ustride + rp_idx(r, H1p, j)) * 4) : 0x7fffffff,
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ru, ok ? (int)((h * ustride + rp_index(r, H1p, j)) * 4) : 0x7fffffff,
                                                          0, 0));
       }
 #pragma unroll
@@ -1149,7 +1068,7 @@ int critic_update_launch(const CritUpdArgs& a, hipStream_t st) {
   RLMD_CHECK(a.draw.n == 0 || (a.draw.idx_out && a.draw.B <= RLMD_MAX_BATCH && a.draw.M > kSortPopulation),
              "critic update: the draw role takes the hash path only");
   const dim3 grid(2 * (a.n_w2 + a.n_w1 + a.ti) + (a.cstats.B > 0 ? 2 : 0) + a.draw.n);
-  const bool split = !RLMD_SPLIT_SPEC || a.loss.qsplit > 1;
+  const bool split = a.loss.qsplit > 1;
 #define CRIT_LAUNCH(P_, W_)                                                                                  \
   do {                                                                                                       \
     if (split) hipLaunchKernelGGL((critic_update_kernel<P_, W_, true>), grid, dim3(NT), ULds::total, st, a);  \

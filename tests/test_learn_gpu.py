@@ -223,6 +223,19 @@ def test_bf16_matches_bf16_oracle(dev, algo, S, A, h1, h2, B, k, loss):
     bf16_vs_oracle(algo, S, A, h1, h2, B, k, loss)
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_narrow_tiles_ragged_edges(dev, precision):
+    """The fused update kernels' 32 x 32 tile form (256 < B <= 512) where its bound
+    checks bite: widths 48 / 40 are no multiples of 32 (partial tiles, zero padding
+    in the copies), and B = 272 is 17 full 16-row blocks, so wave 4's 64-row slice
+    holds one block and waves 5-7 none."""
+    case = ("SAC", 5, 1, 48, 40, 272, 136, "MSE")
+    if precision == "fp32":
+        test_full_size_fp32_matches_oracle(dev, *case)
+    else:
+        bf16_vs_oracle(*case)
+
+
 @pytest.mark.parametrize("algo,S,A,h1,h2,B,k", FULL[:2])
 @pytest.mark.parametrize("loss", ["MSE", "HUB"])
 def test_bf16_launch_chain_matches_bf16_oracle(dev, monkeypatch, algo, S, A, h1, h2, B, k, loss):
