@@ -33,6 +33,15 @@ RLMD_NO_FUSED_ACTOR=1, and every B > 512): dh1 = [h1 > 0] (bf16(dh2) @ bf16(W2))
 (rows.hip cbwd_rows / abwd_rows), dL/da through bf16(dq w3 [h2 > 0]), and the
 weight-gradient GEMM's bf16 operands: dW = bf16(G)^T bf16(X), db = sum bf16(G)
 (gemm.hip GEMM_BWD_W, the bias as a ones column).
+actor_path (default: path) picks the actor half's form on its own: the device
+pairs the fused critic step with the launch-chain actor step when the critic
+input fits the fused kernels (S + A <= 8, B <= 512) and the actions do not
+(A > 2).  path="fused", actor_path="chain" restates that pairing: the critic
+half rounds as under "critic" above (the target path and both forwards are the
+same in every form), the actor half as the chain does: dL/da through
+bf16(dq_new w3 [e2 > 0]) @ bf16(W2) (abwd_rows, not qeval_rows' unit-dq basis),
+dh1 = [h1 > 0] (bf16(dh2) @ bf16(W2)), and dW = bf16(G)^T bf16(X),
+db = sum bf16(G) for every actor layer (heads: G = the head gradients gh).
 """
 import math
 
@@ -197,13 +206,15 @@ class OracleLearner:
                  max_action=0.99, ls_min=-20.0, ls_max=2.0, reparam_noise=1e-6, log_noise=1e-6,
                  cauchy=1.0, logtemp=0.0, policy_noise=0.1, target_noise=0.2, target_clip=0.5,
                  actor_interval=None, target_critic_update=None, target_actor_update=2,
-                 temp_interval=1, actor_topk=True, s_dist="N", precision="fp32", explicit=None, path="fused"):
+                 temp_interval=1, actor_topk=True, s_dist="N", precision="fp32", explicit=None, path="fused",
+                 actor_path=None):
         sac = algo == "SAC"
         # explicit gradients (the kernels' rounding points when bf16); fp32 keeps
         # autograd unless explicit=True (the CPU check that both forms agree)
         self.bf = rbf if precision == "bf16" else ident
         self.explicit = precision == "bf16" if explicit is None else explicit
         self.path = path
+        self.actor_path = path if actor_path is None else actor_path  # the actor half's form
         self.s_dist = s_dist
         self.algo, self.S, self.A, self.B, self.k, self.lt = algo, S, A, B, k, loss_type
         self.lay, self.n = layout(algo, S, A, h1, h2)
@@ -511,7 +522,7 @@ class OracleLearner:
                 dlp = -alpha * dv
             else:
                 dqn = [dv]
-            if self.path == "chain":  # abwd_rows: dq scaled inside the bf16 operand
+            if self.actor_path == "chain":  # abwd_rows: dq scaled inside the bf16 operand
                 da = sum((e1 > 0).float() * (bf((e2 > 0).float() * (d_[:, None] * p["q_value.weight"][0]))
                                              @ bf(p["fc2.weight"])) @ p["fc1.weight"][:, S:]
                          for d_, (p, e1, e2) in zip(dqn, fwq))
@@ -526,7 +537,7 @@ class OracleLearner:
             wh = [pa[h + ".weight"] for h in ah]  # [A, H2] each
             m2a = (h2a > 0).float()
             dh2 = m2a * sum(g_ @ w_ for g_, w_ in zip(gh, wh))
-            if self.path == "chain":  # abwd_rows dh1 + the weight-gradient GEMM
+            if self.actor_path == "chain":  # abwd_rows dh1 + the weight-gradient GEMM
                 dh1 = (h1a > 0).float() * (bf(dh2) @ bf(pa["fc2.weight"]))
                 grads = {"fc1.weight": bf(dh1).T @ bf(s), "fc1.bias": bf(dh1).sum(0),
                          "fc2.weight": bf(dh2).T @ bf(h1a), "fc2.bias": bf(dh2).sum(0)}

@@ -218,7 +218,12 @@ struct ElemMap {
 };
 __device__ __forceinline__ ElemMap elem_map(int Hp) {
   const int tpc = NT / Hp > 0 ? NT / Hp : 1;
-  const int nr = (R + tpc - 1) / tpc;
+  // rows per thread: ceil(R / tpc) rounded up to a power of two, R over the
+  // largest power of two in tpc (tpc <= 16 = R).  The packed stores of layer 1
+  // (m1_index mask words, store_rp_rows) take 1, 2, 4, 8 or 16 rows from a
+  // multiple of that count.  Only Hp = 160 (3 threads per column, 6 rows) rounds:
+  // two of its threads then take 8 rows each, the third none
+  const int nr = R >> (31 - __builtin_clz((unsigned)tpc));
   const int grp = threadIdx.x / Hp;
   ElemMap m;
   m.c = threadIdx.x % Hp;

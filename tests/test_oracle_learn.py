@@ -58,17 +58,20 @@ def test_learn_steps_match_reference(golden, case):
         np.testing.assert_allclose(L.T.numpy(), ref_t, rtol=0, atol=2e-6, err_msg=f"{case} step {s} targets")
 
 
-@pytest.mark.parametrize("path", ["fused", "chain"])
+@pytest.mark.parametrize("path", ["fused", "chain", "fused+chain"])
 @pytest.mark.parametrize("case", ["case0", "case1", "case2", "case3", "case4", "case5", "case6"])
 def test_explicit_gradients_match_reference(golden, case, path):
     """The explicit-gradient form (precision="bf16"'s structure with the rounding
     off) reproduces the reference's learn() like the autograd form: it pins every
-    hand-written gradient formula the bf16 oracle uses."""
+    hand-written gradient formula the bf16 oracle uses.  "fused+chain" is
+    path="fused" with actor_path="chain": the fused critic step's formulas with
+    the launch chain's actor step (the device's pairing for A > 2, S + A <= 8)."""
+    path, _, actor_path = path.partition("+")
     g = golden("learn.npz")
     algo, (S, A, h1, h2, B, k), lay, n, p, t = build(g, case)
     lt = str(g[case + "/loss_fn"])
     L = ol.OracleLearner(algo, S, A, h1, h2, B, k, lt, p, t, s_dist=str(g[case + "/s_dist"]), explicit=True,
-                         path=path)
+                         path=path, actor_path=actor_path or None)
     rep = {x: g[f"{case}/replay/{x}"] for x in ("state", "action", "reward", "next_state", "done")}
     for s in range(int(g[case + "/n_steps"])):
         idx = g[f"{case}/step{s}/idx"]
@@ -107,3 +110,25 @@ def test_bf16_mode_rounds_and_stays_close(golden):
     assert d.max() > 0
     assert np.mean(d < 1e-4) > 0.9
     np.testing.assert_allclose(l16[:6], l32[:6], rtol=5e-2)
+
+
+def test_actor_path_changes_the_actor_half_only(golden):
+    """precision="bf16", path="fused", actor_path="chain": the critic half is
+    path="fused"'s to the bit (same parameters after the critic step), the actor
+    half rounds as the chain does, so its parameters differ from path="fused"'s."""
+    g = golden("learn.npz")
+    algo, (S, A, h1, h2, B, k), lay, n, p, t = build(g, "case0")
+    lt = str(g["case0/loss_fn"])
+    rep = {x: g[f"case0/replay/{x}"] for x in ("state", "action", "reward", "next_state", "done")}
+    idx = g["case0/step0/idx"]
+    args = [rep["state"][idx], rep["action"][idx], rep["reward"][idx], rep["next_state"][idx], rep["done"][idx]]
+    ea, eb = (g["case0/step0/eps_next"], g["case0/step0/eps_cur"]) if algo == "SAC" else (g["case0/step0/eps_target"], None)
+    out = {}
+    for name, kw in (("fused", {}), ("mixed", {"actor_path": "chain"}), ("chain", {"path": "chain"})):
+        L = ol.OracleLearner(algo, S, A, h1, h2, B, k, lt, p, t, precision="bf16", actor_interval=1, **kw)
+        L.learn(*args, ea, eb)
+        out[name] = L.P.numpy().copy()
+    c0 = lay["critic_1"][0][2]
+    np.testing.assert_array_equal(out["mixed"][c0:], out["fused"][c0:])
+    assert np.any(out["mixed"][:c0] != out["fused"][:c0])
+    assert np.any(out["chain"][c0:] != out["fused"][c0:])

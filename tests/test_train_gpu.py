@@ -115,8 +115,12 @@ def _flat_init(algo, S, A, h1, h2, init):
     return p, t
 
 
-@pytest.mark.parametrize("algo,S,A,h1,h2", [("SAC", 5, 1, 256, 256), ("TD3", 6, 2, 400, 300), ("SAC", 6, 4, 256, 256)])
+@pytest.mark.parametrize("algo,S,A,h1,h2", [("SAC", 5, 1, 256, 256), ("TD3", 6, 2, 400, 300), ("SAC", 6, 4, 256, 256),
+                                            ("SAC", 16, 4, 256, 256), ("SAC", 17, 3, 64, 48)])
 def test_act_matches_oracle_policy(dev, algo, S, A, h1, h2):
+    """fp32 acting (the GEMM forward + actor_head_kernel) against the oracle's policy;
+    16/4 and 17/3 are the widest observation the fused bf16 kernel takes and the
+    first it does not, 64/48 a net no fused instantiation covers."""
     from rlmd_amd.agent import DeviceAgent, reference_init
 
     init = reference_init(algo, S, A, h1, h2, seed=2)
@@ -173,12 +177,15 @@ def test_act_policy_dists_match_oracle(dev, dist, precision):
     assert torch.isfinite(phil).all() and (phil.abs() <= ora.max_action).all()
 
 
-def _bf16_act_reference(p, obs, eps, algo, max_action, ls_min, ls_max, noise):
+def _bf16_act_reference(p, obs, eps, algo, max_action, ls_min, ls_max, noise, round_l1=False):
     """The fused bf16 acting numerics restated in torch: layer 1 in f32, its output and
-    fc2.weight rounded to bf16 (RNE), f32 accumulation, f32 heads and sampling."""
+    fc2.weight rounded to bf16 (RNE), f32 accumulation, f32 heads and sampling.
+    round_l1: layer 1's operands (observations, fc1.weight) rounded to bf16 too, as the
+    generic path's GEMM rounds them."""
     import torch.nn.functional as F
 
-    h1 = F.relu(F.linear(obs, p["fc1.weight"], p["fc1.bias"])).bfloat16().float()
+    x, w1 = (obs.bfloat16().float(), p["fc1.weight"].bfloat16().float()) if round_l1 else (obs, p["fc1.weight"])
+    h1 = F.relu(F.linear(x, w1, p["fc1.bias"])).bfloat16().float()
     h2 = F.relu(F.linear(h1, p["fc2.weight"].bfloat16().float(), p["fc2.bias"]))
     head = "pi" if algo == "SAC" else "mu"
     mu = F.linear(h2, p[head + ".weight"], p[head + ".bias"])
@@ -190,14 +197,24 @@ def _bf16_act_reference(p, obs, eps, algo, max_action, ls_min, ls_max, noise):
 
 
 @pytest.mark.parametrize("algo,S,A,h1,h2", [("SAC", 5, 1, 256, 256), ("SAC", 6, 2, 256, 256), ("TD3", 5, 1, 256, 256),
-                                            ("SAC", 5, 1, 128, 256), ("TD3", 6, 2, 400, 300), ("TD3", 5, 1, 400, 300)])
-def test_fused_bf16_act_matches_emulated_reference(dev, algo, S, A, h1, h2):
+                                            ("SAC", 5, 1, 128, 256), ("TD3", 6, 2, 400, 300), ("TD3", 5, 1, 400, 300),
+                                            ("SAC", 8, 2, 256, 256), ("SAC", 9, 2, 256, 256), ("SAC", 5, 3, 256, 256),
+                                            ("SAC", 16, 4, 256, 256), ("TD3", 12, 3, 400, 300), ("SAC", 6, 4, 128, 256),
+                                            ("TD3", 16, 4, 128, 256)])
+def test_fused_bf16_act_matches_emulated_reference(dev, algo, S, A, h1, h2, generic=False):
     """act.hip (one launch: VALU layer 1, bf16 MFMA layer 2, fused heads + sampling)
     against the same numerics restated in torch (bf16 rounding emulated exactly).  The
     f32 accumulation order of layer 1 differs, which now and then flips one h1 element
     to the neighbouring bf16 value: >= 99.9% of actions within 1e-4, all within 1e-3.
     The ragged last block (4099 rows) exercises the row guard; TD3 400/300 the
-    zero-padded K (416) and column (320) tails of the compute copy."""
+    zero-padded K (416) and column (320) tails of the compute copy.
+    fused_act_kernel<H1P, NB, SP, MA, WPC> by shape: S = 8 | 9 is SP = 8 | 16 (the last
+    full and the first padded layer-1 K tile), A = 2 | 3 is MA = kMaxA | kMaxA4 (twice the
+    head registers and partials); 16/4 both at their limits at H1P 256, 12/3 at H1P 416
+    (no LDS aliasing), 6/4 and 16/4 at H1P 128.  The fused env kernels run the same body
+    (test_fused_equals_unfused ties them to it bit for bit).
+    generic: the shape must fall to agent_act's generic path instead (see
+    test_generic_bf16_act_matches_emulated_reference)."""
     from rlmd_amd.agent import DeviceAgent, reference_init
 
     init = reference_init(algo, S, A, h1, h2, seed=3)
@@ -210,17 +227,39 @@ def test_fused_bf16_act_matches_emulated_reference(dev, algo, S, A, h1, h2):
     eps = torch.from_numpy(rng.standard_normal((n, A)).astype(np.float32))
     Pn = ora.nets(ora.P)
     ref_det, ref_sto = _bf16_act_reference(Pn["actor"], obs, eps, algo, ora.max_action, ora.ls_min, ora.ls_max,
-                                           ora.policy_noise)
+                                           ora.policy_noise, round_l1=generic)
     with torch.no_grad():
         det = ag.act(obs, mode=1).cpu()
         sto = ag.act(obs, mode=0, eps=eps).cpu()
         sto_philox = ag.act(obs, mode=0).cpu()
-    for got, ref in ((det, ref_det), (sto, ref_sto)):
+    for name, got, ref in (("deterministic", det, ref_det), ("injected noise", sto, ref_sto)):
         err = (got - ref).abs()
+        print(f"{algo} {S}/{A} {h1}/{h2} {name}: within 1e-4 {(err <= 1e-4).float().mean().item():.6f}, "
+              f"max {err.max().item():.3g}")
         assert (err <= 1e-4).float().mean().item() >= 0.999, err.max().item()
         assert err.max().item() <= 1e-3
     assert torch.isfinite(sto_philox).all() and (sto_philox.abs() <= ora.max_action).all()
     assert not torch.equal(sto_philox, det)
+
+
+@pytest.mark.parametrize("algo,S,A,h1,h2", [("SAC", 17, 2, 256, 256), ("TD3", 5, 1, 64, 48)])
+def test_generic_bf16_act_matches_emulated_reference(dev, algo, S, A, h1, h2):
+    """bf16 acting at shapes no fused_act_kernel instantiation takes (S > 16; H1p 64):
+    agent_act's generic branch, two launches of the MFMA GEMM (gemm.hip GEMM_FWD) and
+    actor_head_kernel, against its rounding points restated in torch.  The GEMM stages
+    BOTH operands of BOTH layers through f2bf (RNE) into LDS (TileRegs::store): layer 1
+    is relu(bf16(obs) bf16(W1)^T + b1), layer 2 relu(bf16(h1) bf16(W2)^T + b2); products
+    of two bf16 values are exact in f32, the MFMA accumulates in f32, bias and ReLU are
+    f32 (store_c) and h1 / h2 are stored as f32.  actor_head_kernel then forms the head
+    dot products, the sampling and tanh in f32 from f32 parameters.  So against the
+    fused kernel's restatement only layer 1's operands are rounded in addition.  The
+    same 4,099 rows (the 64 x 64 tile form of M > 1024 with a ragged last tile), the same
+    bounds: the K-sum order differs from torch's, which now and then flips one h1
+    element to the neighbouring bf16 value."""
+    # the shapes must reach the generic branch: fused_act_supported's conditions, restated
+    h1p, nb = (h1 + 31) // 32 * 32, (h2 + 63) // 64
+    assert not ((h1p, nb) in ((128, 4), (256, 4), (416, 5)) and A <= 4 and S <= 16)
+    test_fused_bf16_act_matches_emulated_reference(dev, algo, S, A, h1, h2, generic=True)
 
 
 @pytest.mark.parametrize("algo,S,A", [("SAC", 5, 1), ("SAC", 6, 2), ("TD3", 5, 1)])
