@@ -413,7 +413,7 @@ struct ActEnvKargs {
   StatFold sf;
 };
 
-template <int FAM, int NG, int H1P, int NB, int SP, int MA, int WPC>
+template <int FAM, int NG, int H1P, int NB, int SP, int MA, int WPC, bool HALF>
 __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA ? WPC : 2) : 1) act_env_kernel(rlmd::FusedActArgs a, EnvParams P, uint32_t step,
                                                       float* obs, rlmd::ReplayView rb, int64_t ring_base,
                                                       StatFold sf) {
@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(256, H1P == 256 ? (MA == rlmd::actrows::kMaxA 
     replay_row_scalars(rb, b, row, o);
     lane_reset_or_commit<FAM>(P, b, o, t, ep, obs, st_n, st_r, st_t);
   };
-  rlmd::actrows::act_rows<H1P, NB, SP, MA, PARK>(a, smem, pro, epi, park);
+  rlmd::actrows::act_rows<H1P, NB, SP, MA, rlmd::actrows::act_nh(MA, HALF), PARK>(a, smem, pro, epi, park);
   block_stats_out(sf, st_n, st_r, st_t);
 }
 
@@ -751,8 +751,8 @@ __global__ void __launch_bounds__(256) eval_market_loop_kernel(rlmd::FusedActArg
                                                    obs_s[j * SP + 4 * ks + kl], h, 0, 0, 0);
         const f32x4 bias = *reinterpret_cast<const f32x4*>(&b1s[16 * tt + 4 * kl]);
         uint2 pk;
-        pk.x = (uint32_t)f2bf_rne(fmaxf(h[0] + bias[0], 0.f)) | ((uint32_t)f2bf_rne(fmaxf(h[1] + bias[1], 0.f)) << 16);
-        pk.y = (uint32_t)f2bf_rne(fmaxf(h[2] + bias[2], 0.f)) | ((uint32_t)f2bf_rne(fmaxf(h[3] + bias[3], 0.f)) << 16);
+        pk.x = f2bf_pk(fmaxf(h[0] + bias[0], 0.f), fmaxf(h[1] + bias[1], 0.f));
+        pk.y = f2bf_pk(fmaxf(h[2] + bias[2], 0.f), fmaxf(h[3] + bias[3], 0.f));
         *reinterpret_cast<uint2*>(&h1s[j * HP + 16 * tt + 4 * kl]) = pk;
       }
     }
@@ -1080,11 +1080,18 @@ int env_act_train(rlmd_env_t env, const ReplayView& rb, int64_t ring_base, uint3
   RLMD_CHECK(ng1 || P.fam != RLMD_DICE_SH, "fused acting + env step: dice_sh has one die");
   RLMD_CHECK(sp == 8 || P.fam == RLMD_MARKET, "fused acting + env step: state wider than 8 (market only)");
   const bool wpc4 = actrows::act_wpc(h1p, P.action_dim > actrows::kMaxA ? actrows::kMaxA4 : actrows::kMaxA, grid.x) == 4;
-#define FUSEDW(F, NG, H, B, SP, MA, W)                                                                                  \
-  hipExtLaunchKernelGGL((act_env_kernel<F, NG, H, B, SP, MA, W>), grid, block,                                        \
+#define FUSEDH(F, NG, H, B, SP, MA, W, HALF)                                                                            \
+  hipExtLaunchKernelGGL((act_env_kernel<F, NG, H, B, SP, MA, W, HALF>), grid, block,                                  \
                         actrows::act_lds_bytes(H, SP, MA, actrows::act_park(H, SP, MA, W)) +                            \
                             (actrows::act_park(H, SP, MA, W) ? actrows::kParkBytes : 0), stream,                         \
                         ev_start, ev_stop, 0, a, env->P, step, obs, rb, ring_base, sf)
+  // at most kMaxA live heads (SAC with one action, TD3): the two-action kernels' half-width epilogue
+  const bool half = actrows::act_half_heads(a.algo, a.A);
+#define FUSEDW(F, NG, H, B, SP, MA, W)                                      \
+  do {                                                                      \
+    if (half) FUSEDH(F, NG, H, B, SP, MA, W, (MA) == actrows::kMaxA);       \
+    else FUSEDH(F, NG, H, B, SP, MA, W, false);                             \
+  } while (0)
 #define FUSEDM(F, NG, H, B, SP, MA)                                                           \
   do {                                                                                        \
     if (wpc4) FUSEDW(F, NG, H, B, SP, MA, ((H) == 256 && (MA) == actrows::kMaxA) ? 4 : 3);    \
@@ -1133,6 +1140,7 @@ int env_act_train(rlmd_env_t env, const ReplayView& rb, int64_t ring_base, uint3
 #undef FUSED
 #undef FUSEDM
 #undef FUSEDW
+#undef FUSEDH
   RLMD_LAUNCH_CHECK();
   stat_fold_end(env, ep_stats);
   *launched = true;

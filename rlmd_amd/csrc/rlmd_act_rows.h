@@ -30,9 +30,10 @@ constexpr int kMaxA = 2;   // the headline shapes (one gamble / asset: investors
 constexpr int kMaxA4 = 4;  // the wide-action instantiation (investors C, Dice_SH B / C)
 
 // Workgroups per CU the 256-wide, two-action acting kernels are compiled for (the
-// WPC template argument: launch bounds).  At 3 they hold 140 VGPRs without
-// spills; at 4 (what their LDS allows, act_lds) they fit 128 VGPRs with 8-22
-// dwords spilled.  4 pays only when 3 per CU would leave a second dispatch round:
+// WPC template argument: launch bounds).  At 3 they hold 132-148 VGPRs without
+// spills; at 4 (what their LDS allows, act_lds) they fit 128 VGPRs: the parked
+// 8-float-state instantiations (act_park) without a spill, the 16-float ones
+// with 3-32 dwords spilled.  4 pays only when 3 per CU would leave a second dispatch round:
 // C2's 1,024 blocks (act_env 34.0 -> 32.4 us), not C4's 128 (19.6 -> 20.8 us).
 inline int act_wpc(int h1p, int ma, int64_t blocks) {
   if (h1p != 256 || ma != kMaxA) return 3;
@@ -53,11 +54,22 @@ inline int act_wpc(int h1p, int ma, int64_t blocks) {
 }
 
 
-// RNE f32 -> bf16, NaN kept quiet; branch-free (a select, not a divergent branch)
+// RNE f32 -> bf16, NaN kept quiet; branch-free (a select, not a divergent branch).
+// The integer form (about 7 VALU ops a value): the definition f2bf_pk is held to.
 __device__ __forceinline__ unsigned short f2bf_rne(float f) {
   const unsigned u = __float_as_uint(f);
   const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
   return (unsigned short)((u & 0x7fffffffu) > 0x7f800000u ? ((u >> 16) | 0x40u) : r);
+}
+
+// f2bf_rne(lo) | f2bf_rne(hi) << 16 in one instruction: the compiler's f32 -> bf16
+// conversion is gfx950's v_cvt_pk_bf16_f32, whose bits equal f2bf_rne's for all
+// 2^32 inputs in this library's denormal mode (NaNs, infinities, denormals and
+// ties included: tools/probe/cvt_bf16_probe.hip)
+__device__ __forceinline__ uint32_t f2bf_pk(float lo, float hi) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
 
 
@@ -107,6 +119,10 @@ __host__ __device__ constexpr ActLds act_lds(int h1p, int sp, int ma, bool park 
 // b, act, obs_row) runs on thread r < 64 of each valid row b with the row's
 // actions act[MA] (f32; MA = kMaxA, or kMaxA4 for 3-4 actions: twice the head
 // registers and partials) and its observation in LDS (obs_row[0 .. S)).
+// NH is the number of head slots the epilogue carries (act_nh: the live heads,
+// pi then log_scale, occupy slots [0, nh), nh <= NH <= 2 MA); a slot costs NB
+// weight registers and NB fma per accumulator value, so one-action SAC and TD3
+// (nh <= 2) run at NH = 2 instead of 2 kMaxA.  The partials keep the 2 MA pitch.
 struct NoPark {
   __device__ void operator()() const {}
 };
@@ -122,10 +138,11 @@ constexpr int kParkBytes = kRows * kParkWords * 4;
 __host__ __device__ constexpr bool act_park(int h1p, int sp, int ma, int wpc) {
   return h1p == 256 && sp == 8 && ma == kMaxA && wpc == 4;  // act_lds + kParkBytes fit 40 KB
 }
-template <int H1P, int NB, int SP, int MA, bool PARK, typename ProF, typename EpiF, typename ParkF = NoPark>
+template <int H1P, int NB, int SP, int MA, int NH, bool PARK, typename ProF, typename EpiF, typename ParkF = NoPark>
 __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* smem, ProF pro, EpiF epi,
                                          ParkF park = ParkF()) {
   constexpr int kMaxA = MA;
+  static_assert(NH >= 1 && NH <= 2 * MA, "head slots");
   constexpr int HP = H1P + 8;  // bf16 row pitch: 16-B aligned fragment reads
   constexpr int NT = L1Tiles<H1P>::NT, NTP = L1Tiles<H1P>::NTP;
   constexpr ActLds LY = act_lds(H1P, SP, MA, PARK);
@@ -150,7 +167,7 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
   // excluded element reads 0): no load sits in a branch, whose merge would wait
   // for it (four such waits had serialised this prologue's load round)
   const __amdgpu_buffer_rsrc_t rp = rlmd_rsrc(a.params, 0x7fffffff);
-  float hw[NB][2 * kMaxA];
+  float hw[NB][NH];
   float b2v[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -158,7 +175,7 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
     const bool live = c < H2;
     b2v[nb] = rlmd_ldf(rp, o.b2 + c, live);
 #pragma unroll
-    for (int h = 0; h < 2 * kMaxA; ++h) {
+    for (int h = 0; h < NH; ++h) {
       const int64_t base = h < A ? o.w3 + (int64_t)h * H2 : o.w4 + (int64_t)(h - A) * H2;
       hw[nb][h] = rlmd_ldf(rp, base + c, live && h < nh);
     }
@@ -166,19 +183,33 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
   // the sampling threads' head biases and policy noise (Philox -> f64 Box-Muller):
   // independent of the forward pass, so drawn here, under the load latency, not
   // in the epilogue's tail
-  float mu_b[kMaxA], ls_b[kMaxA], nz[kMaxA];
+  float mu_b[kMaxA], ls_b[kMaxA], ein[kMaxA], nz[kMaxA];
   const __amdgpu_buffer_rsrc_t re = rlmd_rsrc(a.eps_in, a.eps_in ? (int64_t)a.n * A * 4 : 0);
 #pragma unroll
   for (int j = 0; j < kMaxA; ++j) {
     const bool mine = tid < kRows && row0 + tid < a.n && j < A;
     mu_b[j] = rlmd_ldf(rp, o.b3 + j, mine);
     ls_b[j] = rlmd_ldf(rp, o.b4 + j, mine && a.algo == RLMD_SAC);
-    const float ein = rlmd_ldf(re, (int64_t)(row0 + tid) * A + j, mine && a.mode == 0);
-    // drawn by every thread and selected: a draw in a branch overwrote the
-    // register the speculatively issued eps load targets, which waited on it
-    const float drawn = policy_draw(a.algo == RLMD_SAC ? a.dist : RLMD_DIST_N, a.seed, (uint32_t)(row0 + tid), a.ctr,
-                                    a.tag, j);
-    nz[j] = mine && a.mode == 0 ? (a.eps_in ? ein : drawn) : 0.f;
+    ein[j] = rlmd_ldf(re, (int64_t)(row0 + tid) * A + j, mine && a.mode == 0);
+    nz[j] = 0.f;
+  }
+  // drawn where it is consumed: by the wave that holds the sampling rows, for the
+  // live components, when sampling (mode 0) without injected noise; the other
+  // three waves skip a Philox4x32-10 and a Box-Muller pair per component.  The
+  // branch is scalar and holds no load: all three loads above stay outside it,
+  // and the injected noise is selected after it (a draw in a divergent branch
+  // had overwritten the register the speculatively issued eps load targets,
+  // which waited on it)
+  if (__builtin_amdgcn_readfirstlane(wave) == 0 && a.mode == 0 && a.eps_in == nullptr) {
+#pragma unroll
+    for (int j = 0; j < kMaxA; ++j)
+      if (j < A)
+        nz[j] = policy_draw(a.algo == RLMD_SAC ? a.dist : RLMD_DIST_N, a.seed, (uint32_t)(row0 + tid), a.ctr, a.tag, j);
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxA; ++j) {
+    const bool mine = tid < kRows && row0 + tid < a.n && j < A;
+    nz[j] = mine && a.mode == 0 ? (a.eps_in ? ein[j] : nz[j]) : 0.f;
   }
   pro();
   // -- stage W1, b1 and this block's observations into the zero-padded LDS
@@ -289,10 +320,8 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
       for (int u = 0; u < 8; ++u) {
         if (t0 + u < NT) {
           uint2 pk;
-          pk.x = (uint32_t)f2bf_rne(fmaxf(h[u][0] + bias[u][0], 0.f)) |
-                 ((uint32_t)f2bf_rne(fmaxf(h[u][1] + bias[u][1], 0.f)) << 16);
-          pk.y = (uint32_t)f2bf_rne(fmaxf(h[u][2] + bias[u][2], 0.f)) |
-                 ((uint32_t)f2bf_rne(fmaxf(h[u][3] + bias[u][3], 0.f)) << 16);
+          pk.x = f2bf_pk(fmaxf(h[u][0] + bias[u][0], 0.f), fmaxf(h[u][1] + bias[u][1], 0.f));
+          pk.y = f2bf_pk(fmaxf(h[u][2] + bias[u][2], 0.f), fmaxf(h[u][3] + bias[u][3], 0.f));
           *reinterpret_cast<uint2*>(&h1s[ra * HP + 16 * (t0 + u) + 4 * kl]) = pk;
         }
       }
@@ -332,22 +361,22 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
   for (int m = 0; m < 4; ++m) {
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
-      float ph[2 * kMaxA];
+      float ph[NH];
 #pragma unroll
-      for (int h = 0; h < 2 * kMaxA; ++h) ph[h] = 0.f;
+      for (int h = 0; h < NH; ++h) ph[h] = 0.f;
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const float v = fmaxf(acc[m][nb][rg] + b2v[nb], 0.f);
 #pragma unroll
-        for (int h = 0; h < 2 * kMaxA; ++h) ph[h] = fmaf(v, hw[nb][h], ph[h]);
+        for (int h = 0; h < NH; ++h) ph[h] = fmaf(v, hw[nb][h], ph[h]);
       }
 #pragma unroll
-      for (int h = 0; h < 2 * kMaxA; ++h)
+      for (int h = 0; h < NH; ++h)
         if (h < nh) ph[h] = rlmd_row16_sum(ph[h]);
       if ((lane & 15) == 0) {
         const int r = 16 * m + 4 * (lane >> 4) + rg;
 #pragma unroll
-        for (int h = 0; h < 2 * kMaxA; ++h)
+        for (int h = 0; h < NH; ++h)
           if (h < nh) part[(wave * kRows + r) * 2 * kMaxA + h] = ph[h];
       }
     }
@@ -408,6 +437,12 @@ inline size_t act_lds_bytes(int h1p, int sp, int ma = kMaxA, bool park = false) 
 
 // the acting body's action bound for an action count
 inline int act_ma(int action_dim) { return action_dim <= kMaxA ? kMaxA : kMaxA4; }
+
+// the acting body's head slots (NH) at an action bound: the two-action kernels
+// have a half-width instantiation for up to kMaxA live heads (SAC with one
+// action, TD3), the wide ones carry all 2 MA
+constexpr int act_nh(int ma, bool half) { return ma == kMaxA && half ? kMaxA : 2 * ma; }
+inline bool act_half_heads(int algo, int action_dim) { return (algo == RLMD_SAC ? 2 : 1) * action_dim <= kMaxA; }
 
 }  // namespace actrows
 }  // namespace rlmd
