@@ -4,7 +4,9 @@
 // small per-row MLP evaluations separated by a few batch-wide reductions.  Every
 // per-row stretch of that chain runs here inside ONE 16-row workgroup of 8 waves,
 // so intermediate activations never round-trip through a kernel boundary:
-//   layer 1   VALU: thread = (hidden unit, row group), x rows broadcast from LDS
+//   layer 1   v_mfma_f32_16x16x4f32 over the (up to 8, zero padded) inputs, wave w
+//             owning unit bands w, w + 8, ...; wider states on the VALU: thread =
+//             (hidden unit, row group), x rows broadcast from LDS
 //   layer 2   v_mfma_f32_16x16x32_bf16 (bf16) / v_mfma_f32_16x16x4f32 (fp32):
 //             A = the 16 activation rows in LDS, B = fc2.weight fragments read
 //             16 bytes per lane straight from the zero-padded compute copy
@@ -33,7 +35,8 @@ constexpr int R = kRowBlock;  // rows per workgroup
 constexpr int NT = 512;       // threads per workgroup
 constexpr int NW = NT / 64;   // waves
 constexpr int NHF = 4;        // heads reduced in the MFMA epilogue (more -> LDS dot products)
-constexpr int W1P = 8;        // fc1 inputs preloaded per thread (more -> read in the loop)
+constexpr int W1P = 8;        // fc1 inputs of the MFMA layer 1 (two K-steps); wider states: preloaded
+                              // per thread on the VALU path (more -> read in the loop)
 constexpr int kHeadsMax = 2 * RLMD_MAX_ACTION;
 
 #ifdef RLMD_TIMING
@@ -45,22 +48,27 @@ __device__ unsigned long long g_ts_rows[128];
 // job windows (constant-rate clock, comparable across workgroups): block x = 0
 #define RLMD_TSJ(i) RLMD_STAMP(threadIdx.x == 0 && blockIdx.x == 0, g_ts_rows[i], __builtin_amdgcn_s_memrealtime())
 
-// f32 -> bf16 in integer arithmetic: round to nearest even, a NaN keeps its high
-// payload bits with the quiet bit set.  Not update.hip's bf16_rne (the hardware
-// convert): other instructions and another NaN payload, so the two stay apart.
-__device__ __forceinline__ unsigned short to_bf16(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-
-// the row kernels' precision trait: the shared MFMA step and the operand convert
+// the row kernels' precision trait: the shared MFMA step and the operand convert.
+// f32 -> bf16 is the packed hardware convert (f2bf_pk, rlmd_mfma.h): round to
+// nearest even, a NaN keeps its high payload bits with the quiet bit set — the
+// bits of the integer form (f2bf_rne) these kernels computed per value before.
 template <int PREC>
 struct CT : Mfma<PREC> {
-  __device__ __forceinline__ static typename Mfma<PREC>::T cvt(float f) {
-    if constexpr (PREC == RLMD_BF16) return to_bf16(f);
+  using T = typename Mfma<PREC>::T;
+  __device__ __forceinline__ static T cvt(float f) {
+    if constexpr (PREC == RLMD_BF16) return (unsigned short)f2bf_pk(f, 0.f);
     else return f;
+  }
+  // two values at once: one instruction in bf16
+  __device__ __forceinline__ static void cvt2(float lo, float hi, T& a, T& b) {
+    if constexpr (PREC == RLMD_BF16) {
+      const uint32_t pk = f2bf_pk(lo, hi);
+      a = (unsigned short)pk;
+      b = (unsigned short)(pk >> 16);
+    } else {
+      a = lo;
+      b = hi;
+    }
   }
 };
 
@@ -246,9 +254,16 @@ __device__ __forceinline__ int acc_row(int rg) { return 4 * ((threadIdx.x & 63) 
 // forward pieces
 // ---------------------------------------------------------------------------
 // per-thread constants of one net's forward, loaded before any compute
+// layer 1 runs on the f32 MFMA when every input fits two K-steps of 4
+__device__ __forceinline__ bool l1_mfma(int in) { return in <= W1P; }
+
 template <int NBW>
 struct FwdConst {
-  float w1[W1P], b1;    // fc1 row of this thread's hidden unit
+  // fc1 as layer1() takes it.  l1_mfma(in): the MFMA operands of this lane's
+  // accumulator columns over H1p, w1[2 i + s] = W1[acc_col(i)][4 s + (lane >> 4)]
+  // (zero past in) and b1[i] that column's bias.  Wider inputs (the VALU map):
+  // the first W1P inputs of elem_map's hidden unit and its bias in b1[0]
+  float w1[W1P], b1[NBW];
   float b2[NBW];        // fc2 bias of this lane's accumulator columns
   float hw[NBW][NHF];   // head weights of those columns (nh <= NHF)
 };
@@ -256,25 +271,41 @@ struct FwdConst {
 template <int NBW>
 __device__ __forceinline__ void fwd_const(FwdConst<NBW>& k, const float* p, const NetOff& o, int in, int nh,
                                           const float* wa, const float* wb, int na, int nb0 = 0) {
-  const ElemMap m = elem_map(pad32(o.h1));
-  const bool own = m.c < o.h1 && m.r0 < R;
   const __amdgpu_buffer_rsrc_t rp = rlmd_rsrc(p, o.size * 4);
-  // j < in and h < nh are uniform: skipped loads are not issued (a wave holds at
-  // most 63 loads in flight, and the first load round is at that limit)
-  // the fc1 row (in <= 8 contiguous floats) as one or two 16-B loads: a wave's
-  // 64 consecutive units are one 1.5 KB span, and per-float loads touched its
-  // cache lines once per input (the load round is bound by line accesses)
-  {
+  // 4 s < in, j < in and h < nh are uniform: skipped loads are not issued (a wave
+  // holds at most 63 loads in flight, and the first load round is at that limit)
+  static_assert(2 * NBW <= W1P, "the MFMA operands of layer 1 share w1's registers");
+#pragma unroll
+  for (int j = 0; j < W1P; ++j) k.w1[j] = 0.f;
+#pragma unroll
+  for (int i = 0; i < NBW; ++i) k.b1[i] = 0.f;
+  if (l1_mfma(in)) {
+    // one float per (band, K-step): the lanes of a K row read 16 consecutive
+    // units' rows (a 16 in-float span), the four K rows the same lines
+    const int kq = ((int)threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int i = 0; i < NBW; ++i) {
+      const int col = acc_col(i);
+      const bool cin = col < o.h1;
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (4 * s < in) k.w1[2 * i + s] = rlmd_ldf(rp, o.w1 + (int64_t)col * in + 4 * s + kq, cin && 4 * s + kq < in);
+      k.b1[i] = rlmd_ldf(rp, o.b1 + col, cin);
+    }
+  } else {
+    // the first W1P inputs of the fc1 row as two 16-B loads: a wave's 64
+    // consecutive units are one span, and per-float loads touched its cache
+    // lines once per input (the load round is bound by line accesses)
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const ElemMap m = elem_map(pad32(o.h1));
+    const bool own = m.c < o.h1 && m.r0 < R;
     const int off = (int)((o.w1 + (int64_t)m.c * in) * 4);
     const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(rp, own ? off : 0x7fffffff, 0, 0);
-    u32x4 hi = u32x4{0u, 0u, 0u, 0u};
-    if (in > 4) hi = __builtin_amdgcn_raw_buffer_load_b128(rp, own ? off + 16 : 0x7fffffff, 0, 0);
+    const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(rp, own ? off + 16 : 0x7fffffff, 0, 0);
 #pragma unroll
-    for (int j = 0; j < W1P; ++j)
-      k.w1[j] = j < in ? __builtin_bit_cast(float, j < 4 ? lo[j & 3] : hi[j & 3]) : 0.f;
+    for (int j = 0; j < W1P; ++j) k.w1[j] = __builtin_bit_cast(float, j < 4 ? lo[j & 3] : hi[j & 3]);
+    k.b1[0] = rlmd_ldf(rp, o.b1 + m.c, own);
   }
-  k.b1 = rlmd_ldf(rp, o.b1 + m.c, own);
   const int64_t oa = wa - p, ob = (wb ? wb : wa) - p;  // head rows relative to p
 #pragma unroll
   for (int i = 0; i < NBW; ++i) {
@@ -346,11 +377,71 @@ __device__ __forceinline__ void store_rp_rows(typename CT<PREC>::T* base, int64_
   }
 }
 
-// h1 = relu(x W1^T + b1): A operand (T, zero-padded to H1p) + f32 to HBM (nullable)
+// h1 = relu(x W1^T + b1): A operand (T, zero-padded to H1p) + f32 to HBM (nullable).
+//
+// Up to W1P inputs (l1_mfma) the [16 x H1p x 8] product runs on the f32 MFMA
+// (v_mfma_f32_16x16x4f32, two K-steps): wave w owns unit bands w, w + 8, ... as in
+// layer 2, A = the x rows (one 4-byte LDS read per K-step per lane), B = k.w1.
+// The instruction is an fmaf chain over ascending k from the zero accumulator —
+// the dot the VALU form computed per (unit, row) — so the bits are unchanged;
+// the bias is added after it.  A lane ends with 4 rows of one unit per band: the
+// accumulator layout the mask word (m1_index) and the row-packed h1 are stored in.
+template <int PREC, int NBW>
+__device__ __forceinline__ void layer1_mfma(const FwdConst<NBW>& k, const NetOff& o, const float* xs, int ldx,
+                                            typename CT<PREC>::T* a1, int lda1, float* h1_out, uint8_t* m1_out,
+                                            int row0, int B, const FwdExtra<PREC>* ex) {
+  using T = typename CT<PREC>::T;
+  const int H1 = o.h1, H1p = pad32(H1);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // xs rows are zero padded to ldx >= W1P: both K-steps read unconditionally
+  const float x0 = xs[(lane & 15) * ldx + (lane >> 4)], x1 = xs[(lane & 15) * ldx + 4 + (lane >> 4)];
+#pragma unroll
+  for (int i = 0; i < NBW; ++i) {
+    if (wave + NW * i < H1p / 16) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, k.w1[2 * i], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, k.w1[2 * i + 1], acc, 0, 0, 0);
+      const int col = acc_col(i), r0 = acc_row(0);
+      const bool cin = col < H1;
+      float v[4];
+      uint32_t mw = 0;
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        v[rg] = cin ? fmaxf(acc[rg] + k.b1[i], 0.f) : 0.f;
+        mw |= (v[rg] > 0.f ? 1u : 0u) << (8 * rg);
+      }
+      T t[4];
+      CT<PREC>::cvt2(v[0], v[1], t[0], t[1]);
+      CT<PREC>::cvt2(v[2], v[3], t[2], t[3]);
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        a1[(r0 + rg) * lda1 + col] = t[rg];
+        if (h1_out && cin && row0 + r0 + rg < B) h1_out[(int64_t)(row0 + r0 + rg) * H1 + col] = v[rg];
+        if (ex && ex->m1s) ex->m1s[(r0 + rg) * H1p + col] = (uint8_t)((mw >> (8 * rg)) & 1u);
+      }
+      if (m1_out) rlmd_st_wt(reinterpret_cast<uint32_t*>(m1_out + m1_index(row0 / R, H1p, r0, col)), mw);
+      if (ex && ex->hp1) {
+        // h1 in the compute type as the A operand holds it, rows past B zero
+        T hz[4];
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) hz[rg] = row0 + r0 + rg < B ? t[rg] : T(0);
+        store_rp_rows<PREC, 4>(ex->hp1, rp_index(row0 / R, H1p, r0, col), hz, 4);
+      }
+    }
+  }
+}
+
+// States wider than W1P floats: thread = (hidden unit, row group), x rows
+// broadcast from LDS, an fmaf chain over the `in` inputs (a K padded to a
+// multiple of 4 would append fma(0, 0, acc) steps, which turn a -0 sum into +0).
 template <int PREC, int NBW>
 __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, const NetOff& o, const float* xs,
                                        int ldx, int in, typename CT<PREC>::T* a1, int lda1, float* h1_out,
                                        uint8_t* m1_out, int row0, int B, const FwdExtra<PREC>* ex = nullptr) {
+  if (l1_mfma(in)) {
+    layer1_mfma<PREC, NBW>(k, o, xs, ldx, a1, lda1, h1_out, m1_out, row0, B, ex);
+    return;
+  }
   constexpr int MR = kMR<NBW>;
   const int H1 = o.h1, H1p = pad32(H1);
   const ElemMap m = elem_map(H1p);
@@ -362,7 +453,7 @@ __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, c
     const int r = m.r0 + rr;
     float v = 0.f;
     if (m.c < H1) {
-      v = fmaxf(acc + k.b1, 0.f);
+      v = fmaxf(acc + k.b1[0], 0.f);
       if (h1_out && row0 + r < B) h1_out[(int64_t)(row0 + r) * H1 + m.c] = v;
     }
     a1[r * lda1 + m.c] = CT<PREC>::cvt(v);
@@ -375,49 +466,16 @@ __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, c
       mk[0] |= bit;
     }
   };
-  if (in <= W1P && (ldx & 3) == 0) {
-    // every input in registers (k.w1, zero past in): a batch of rows' xs as 16-byte
-    // LDS reads issued together, then their dots (j ascending, as below).  The
-    // per-row loop waited one LDS round trip per row, its bounds being run-time.
-    constexpr int LB = MR < 8 ? MR : 8;
-    static_assert(W1P == 8, "the batched dots below read 8 inputs per row");
+  for (int r = m.r0; r < m.r1; ++r) {
+    float acc = 0.f;
+    if (m.c < H1) {
+      // the first W1P inputs from registers: no branch between their LDS reads,
+      // so they issue together
 #pragma unroll
-    for (int b0 = 0; b0 < MR; b0 += LB) {
-      float4 xv[LB][2];
-#pragma unroll
-      for (int i = 0; i < LB; ++i) {
-        const int r = m.r0 + b0 + i < R ? m.r0 + b0 + i : R - 1;  // rows past this thread's: read, unused
-        xv[i][0] = *reinterpret_cast<const float4*>(xs + r * ldx);
-        xv[i][1] = *reinterpret_cast<const float4*>(xs + r * ldx + 4);
-      }
-#pragma unroll
-      for (int i = 0; i < LB; ++i) {
-        if (b0 + i < nr) {
-          float acc = 0.f;
-          acc = fmaf(xv[i][0].x, k.w1[0], acc);
-          acc = fmaf(xv[i][0].y, k.w1[1], acc);
-          acc = fmaf(xv[i][0].z, k.w1[2], acc);
-          acc = fmaf(xv[i][0].w, k.w1[3], acc);
-          acc = fmaf(xv[i][1].x, k.w1[4], acc);
-          acc = fmaf(xv[i][1].y, k.w1[5], acc);
-          acc = fmaf(xv[i][1].z, k.w1[6], acc);
-          acc = fmaf(xv[i][1].w, k.w1[7], acc);
-          emit(b0 + i, acc);
-        }
-      }
+      for (int j = 0; j < W1P; ++j) acc = fmaf(xs[r * ldx + j], k.w1[j], acc);
+      for (int j = W1P; j < in; ++j) acc = fmaf(xs[r * ldx + j], w[j], acc);
     }
-  } else {
-    for (int r = m.r0; r < m.r1; ++r) {
-      float acc = 0.f;
-      if (m.c < H1) {
-        // xs rows are zero padded to ldx >= W1P and k.w1[j] = 0 for j >= in: no branch
-        // between the LDS reads, so a row's W1P reads issue together
-#pragma unroll
-        for (int j = 0; j < W1P; ++j) acc = fmaf(xs[r * ldx + j], k.w1[j], acc);
-        for (int j = W1P; j < in; ++j) acc = fmaf(xs[r * ldx + j], w[j], acc);
-      }
-      emit(r - m.r0, acc);
-    }
+    emit(r - m.r0, acc);
   }
   if (m.r0 < R) {
     // the mask bytes: one word per 4 rows (m1_index keeps rows 4q..4q+3 of a column together)
@@ -447,8 +505,11 @@ __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, c
 }
 
 // relu(acc + b2) -> HBM (nullable), LDS rows (nullable) and the per-wave head
-// partials part[wave][row][h] (nh <= NHF).
-template <int NBW, int PREC = RLMD_BF16>
+// partials part[wave][row][h] (nh <= NHF).  NH: the head slots carried through
+// the sums (nh <= NH, or nh > NHF: none is written); a slot costs 4 NBW fmaf and a
+// 16-lane sum per row group, so a critic (one head) runs at NH = 1 and one-action
+// SAC / TD3 policies at NH = 2.  Each live head's chain keeps its order.
+template <int NBW, int PREC = RLMD_BF16, int NH = NHF>
 __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBW], const FwdConst<NBW>& k, const NetOff& o,
                                              int nh, float* h2_out, uint8_t* m2_out, float* h2s, int ldh2,
                                              float* part, int row0, int B, const FwdExtra<PREC>* ex = nullptr,
@@ -456,41 +517,50 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBW], const FwdC
   // output bands nb0 .. nb0 + nbw - 1 (a column split; nbw = 0: all of them)
   const int H2 = o.h2, nblk = nbw ? nbw : pad32(H2) / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float ph[4][NHF];
+  using T = typename CT<PREC>::T;
+  float ph[4][NH];
 #pragma unroll
   for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
-    for (int h = 0; h < NHF; ++h) ph[rg][h] = 0.f;
+    for (int h = 0; h < NH; ++h) ph[rg][h] = 0.f;
 #pragma unroll
   for (int i = 0; i < NBW; ++i) {
     if (wave + NW * i < nblk) {
       const int col = acc_col(i, nb0);
       const bool cin = col < H2;
       uint32_t mw = 0;
-      typename CT<PREC>::T hz[4];
+      float v[4];
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         const int r = acc_row(rg);
-        const float v = cin ? fmaxf(acc[i][rg] + k.b2[i], 0.f) : 0.f;
-        if (h2_out && cin && row0 + r < B) h2_out[(int64_t)(row0 + r) * H2 + col] = v;
-        if (h2s) h2s[r * ldh2 + col] = v;
-        // critic basis pass A operand: [h2 > 0] * w3 (the head weight of this column)
-        if (ex && ex->aU) ex->aU[r * lda1 + col] = CT<PREC>::cvt(v > 0.f ? k.hw[i][0] : 0.f);
-        hz[rg] = CT<PREC>::cvt(row0 + r < B ? v : 0.f);
-        mw |= (v > 0.f ? 1u : 0u) << (8 * rg);
+        v[rg] = cin ? fmaxf(acc[i][rg] + k.b2[i], 0.f) : 0.f;
+        if (h2_out && cin && row0 + r < B) h2_out[(int64_t)(row0 + r) * H2 + col] = v[rg];
+        if (h2s) h2s[r * ldh2 + col] = v[rg];
+        mw |= (v[rg] > 0.f ? 1u : 0u) << (8 * rg);
 #pragma unroll
-        for (int h = 0; h < NHF; ++h) ph[rg][h] = fmaf(v, k.hw[i][h], ph[rg][h]);
+        for (int h = 0; h < NH; ++h) ph[rg][h] = fmaf(v[rg], k.hw[i][h], ph[rg][h]);
+      }
+      // critic basis pass A operand: [h2 > 0] * w3 (the head weight of this column, converted once)
+      if (ex && ex->aU) {
+        const T w3c = CT<PREC>::cvt(k.hw[i][0]);
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) ex->aU[acc_row(rg) * lda1 + col] = v[rg] > 0.f ? w3c : T(0);
       }
       if (m2_out) rlmd_st_wt(reinterpret_cast<uint32_t*>(m2_out + rp_index(row0 / R, pad32(H2), acc_row(0), col)), mw);
-      // the lane's 4 rows of h2, contiguous in the row-packed layout
-      if (ex && ex->hp2) store_rp_rows<PREC, 4>(ex->hp2, rp_index(row0 / R, pad32(H2), acc_row(0), col), hz, 4);
+      // the lane's 4 rows of h2 (rows past B zero), contiguous in the row-packed layout
+      if (ex && ex->hp2) {
+        T hz[4];
+        CT<PREC>::cvt2(row0 + acc_row(0) < B ? v[0] : 0.f, row0 + acc_row(1) < B ? v[1] : 0.f, hz[0], hz[1]);
+        CT<PREC>::cvt2(row0 + acc_row(2) < B ? v[2] : 0.f, row0 + acc_row(3) < B ? v[3] : 0.f, hz[2], hz[3]);
+        store_rp_rows<PREC, 4>(ex->hp2, rp_index(row0 / R, pad32(H2), acc_row(0), col), hz, 4);
+      }
     }
   }
-  if (nh <= NHF) {
+  if (nh <= NH) {
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
-      for (int h = 0; h < NHF; ++h) {
+      for (int h = 0; h < NH; ++h) {
         if (h < nh) {
           const float c = rlmd_row16_sum(ph[rg][h]);
           if ((lane & 15) == 0) part[(wave * R + acc_row(rg)) * NHF + h] = c;
@@ -534,7 +604,8 @@ struct NoHook {
 // after_l2 runs right after layer 2's MFMAs, once pre's registers are free: a
 // job issues its NEXT fragment stream there, under this net's epilogue, instead
 // of with the first load round, where it queued behind (and delayed) this one.
-template <int PREC, int NBW, bool MULTI, typename Hook = NoHook>
+// NH: the epilogue's head slots at compile time (a critic: 1); 0: chosen from nh.
+template <int PREC, int NBW, bool MULTI, int NH = 0, typename Hook = NoHook>
 __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, const FwdConst<NBW>& k, Pre<PREC, NBW, MULTI>& pre,
                          const float* xs, int ldx, int in, int nh, const float* wa, const float* wb, int na,
                          unsigned char* smem, const Lds& L, float* h1_out, float* h2_out, int row0, int B,
@@ -562,8 +633,13 @@ __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, con
   if (blockIdx.y == 4) RLMD_TSR(89);
   if (blockIdx.y == 0 && ts >= 0) RLMD_TSR(ts + 2);
   const bool fused = nh <= NHF;
-  fwd_epilogue<NBW, PREC>(acc, k, o, nh, h2_out, m2_out, fused ? nullptr : h2s, L.ldh2, part, row0, B, ex, L.lda1,
-                          nb0, nbw);
+  float* h2d = fused ? nullptr : h2s;
+  if constexpr (NH > 0)
+    fwd_epilogue<NBW, PREC, NH>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
+  else if (nh <= 2)
+    fwd_epilogue<NBW, PREC, 2>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
+  else
+    fwd_epilogue<NBW, PREC, NHF>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
   if (blockIdx.y == 2) RLMD_TSR(66);
   if (blockIdx.y == 4) RLMD_TSR(90);
   if (blockIdx.y == 0 && ts >= 0) RLMD_TSR(ts + 3);
@@ -890,7 +966,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
                   pre_nz);
     __syncthreads();
     RLMD_TSR(16 * job + 4);
-    mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
+    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
                                nullptr, row0, B, nullptr, nullptr, nullptr, nb0, nbw, NoHook(), 22);
     RLMD_TSR(16 * job + 5);
     float* qt = (nxt ? a.qtn[job] : a.qt[job]) + p * B;
@@ -918,7 +994,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     __syncthreads();
     if (job == 2) RLMD_TSR(61);
     if (!upd) {
-      mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.c1[g],
+      mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.c1[g],
                                  a.c2[g], row0, B, a.cm1[g], a.cm2[g], nullptr, nb0, nbw);
     } else {
       using T = typename CT<PREC>::T;
@@ -926,7 +1002,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
       uint8_t* m1s = reinterpret_cast<uint8_t*>(smem + L.m1s);
       // h1 is the same in both halves: half 0 writes it
       const FwdExtra<PREC> ex{p == 0 ? static_cast<T*>(a.hp1[g]) : nullptr, static_cast<T*>(a.hp2[g]), m1s, aU};
-      mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
+      mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
                                  nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw, issue_basis);
       // the backward basis of these rows: U1 = [h1 > 0] * (([h2 > 0] w3) W2), so
       // that the critic update forms dh1 = dq * U1 once dq is known (update.hip);
@@ -1066,10 +1142,11 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     const float wk = rlmd_ldf(rlmd_rsrc(an.p, a.ao.size * 4), wrow + m.c, m.c < d.H2);
     if (blockIdx.x == 0 && m.r0 == 0 && m.c < d.H2) a.wheads[(int64_t)h * d.H2 + m.c] = wk;
     T* aU = reinterpret_cast<T*>(smem + L.aU);
+    const T wkc = CT<PREC>::cvt(wk);  // [h2 > 0] * W_head: the weight or zero, converted once
 #pragma unroll
     for (int rr = 0; rr < kMR<NBW>; ++rr) {
       const int r = m.r0 + rr;
-      if (r < m.r1) aU[r * L.lda1 + m.c] = CT<PREC>::cvt(k.m2[rr] > 0.f ? wk : 0.f);
+      if (r < m.r1) aU[r * L.lda1 + m.c] = k.m2[rr] > 0.f ? wkc : T(0);
     }
     __syncthreads();
     f32x4 acc[NBW];
@@ -1111,7 +1188,7 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
   stage_rows(a.x, d.X, xs, L.ldx, row0, B);
   __syncthreads();
   if (!upd) {
-    mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.e1[g],
+    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.e1[g],
                                a.e2[g], row0, B, a.em1[g], a.em2[g], nullptr, nb0, nbw);
   } else {
     // the critic on (s, a_new) and its input gradient dq/da per row: the basis
@@ -1122,7 +1199,7 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     const uint8_t* m1s = reinterpret_cast<const uint8_t*>(smem + L.m1s);
     float* part = reinterpret_cast<float*>(smem + L.part);
     const FwdExtra<PREC> ex{nullptr, nullptr, reinterpret_cast<uint8_t*>(smem + L.m1s), aU};
-    mlp_rows<PREC, NBW, MULTI>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
+    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
                                nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw, issue_basis);
     f32x4 acc[NBW];
     mfma_rows<PREC, NBW, MULTI>(pw, aU, L.lda1, cn.wt, H2p, ke, H1p / 16, acc, 0, ks0);
@@ -1175,13 +1252,21 @@ __device__ __forceinline__ void dh2_from_q(const BwdMask<NBW>& k, const float* d
   float dq[kMR<NBW>];
 #pragma unroll
   for (int rr = 0; rr < kMR<NBW>; ++rr) dq[rr] = dqr[m.r0 + rr < R ? m.r0 + rr : R - 1];
+  static_assert(kMR<NBW> % 2 == 0, "rows convert in pairs");
 #pragma unroll
-  for (int rr = 0; rr < kMR<NBW>; ++rr) {
-    const int r = m.r0 + rr;
-    if (r < m.r1) {
-      const float v = k.m2[rr] > 0.f ? dq[rr] * k.w3 : 0.f;
-      aT[r * ldaT + m.c] = CT<PREC>::cvt(v);
-      if (dh2_out && m.c < H2 && row0 + r < B) dh2_out[(int64_t)(row0 + r) * H2 + m.c] = v;
+  for (int rr = 0; rr < kMR<NBW>; rr += 2) {
+    float v[2];
+    typename CT<PREC>::T t[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) v[e] = k.m2[rr + e] > 0.f ? dq[rr + e] * k.w3 : 0.f;
+    CT<PREC>::cvt2(v[0], v[1], t[0], t[1]);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int r = m.r0 + rr + e;
+      if (r < m.r1) {
+        aT[r * ldaT + m.c] = t[e];
+        if (dh2_out && m.c < H2 && row0 + r < B) dh2_out[(int64_t)(row0 + r) * H2 + m.c] = v[e];
+      }
     }
   }
 }

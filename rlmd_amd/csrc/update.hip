@@ -77,8 +77,9 @@ __device__ unsigned long long g_ts_aupd[128];
 #define RLMD_TSA(i) RLMD_TS_AT(g_ts_aupd, i)  // actor step
 
 // f32 -> bf16, round to nearest even: the plain cast lowers to v_cvt_pk_bf16_f32
-// (NaN stays NaN; no per-element branch).  Not rows.hip's to_bf16 (integer
-// rounding): other instructions and another NaN payload, so the two stay apart.
+// (NaN stays NaN; no per-element branch): the instruction behind the row kernels'
+// f2bf_pk (rlmd_mfma.h), the same bits for every input, NaN payloads included
+// (tools/probe/cvt_bf16_probe.hip).
 __device__ __forceinline__ unsigned short bf16_rne(float f) {
   return __builtin_bit_cast(unsigned short, (__bf16)f);
 }

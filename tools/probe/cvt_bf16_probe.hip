@@ -1,5 +1,6 @@
 // cvt_bf16_probe.hip — does gfx950's v_cvt_pk_bf16_f32 give the bits of
-// rlmd_act_rows.h's f2bf_rne for every f32?  One kernel over all 2^32 inputs
+// rlmd_mfma.h's f2bf_rne (the integer convert of the acting body and, as to_bf16
+// until round 9, of the row kernels) for every f32?  One kernel over all 2^32 inputs
 // (NaNs, infinities, denormals and ties included), compiled with the library's
 // flags, so it runs in the library's denormal mode.  Candidates per input: the
 // instruction's low half, its high half, the compiler's own f32 -> __bf16 cast,
