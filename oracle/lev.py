@@ -12,8 +12,10 @@ float32; after each step t >= 1 the values are sorted descending, the first
 [mean, mean_top, mean_adj, mad, mad_top, mad_adj, std, std_top, std_adj,
  med, med_top, med_adj, lev] is stored (std unbiased=False, median = the
 lower middle element, as torch.median).  data_T holds the values after all
-`horizon` steps.  Pinned to the reference run on torch CPU
-(tests/golden/lev.npz, make_golden.py:lev_fixtures).
+`horizon` steps.  final_stats is the *_fixed_final_lev family: the same 12
+statistics of the values at maturity only.  Pinned to the reference run on
+torch CPU (tests/golden/lev.npz, lev_edges.npz, lev_final.npz;
+make_golden.py:lev_fixtures, lev_edge_fixtures, lev_final_fixtures).
 """
 import numpy as np
 
@@ -85,33 +87,70 @@ def _levs(lev_low, lev_high, lev_incr, negate):
     return -levs if negate else levs
 
 
+def _gambles(kind, outcomes, rets):
+    """(negate the grid?, g_of_lev) of one gamble family: g_of_lev(lev) -> the
+    f32 factors [investors, horizon].  coin: outcome 1 up, else down, 1 + lev * r;
+    dice: {0 up, 1 down, 2 mid}, 1 + lev * r; dicesh: 1 + lev * r + (1 - lev) * r_sh;
+    gbm: exp(lev * outcome)."""
+    one = np.float32(1)
+    if kind == "gbm":
+        o = outcomes.astype(np.float32)
+        return False, lambda lev: np.exp(lev * o).astype(np.float32)
+    if kind == "coin":
+        up_r, down_r = rets
+        f = lambda lev, r: one + lev * np.float32(r)  # noqa: E731
+        return -down_r > up_r, lambda lev: np.where(outcomes == 1, f(lev, up_r), f(lev, down_r)).astype(np.float32)
+    if kind == "dice":
+        rs = [(r, 0.0) for r in rets]
+        f = lambda lev, r, _: one + lev * np.float32(r)  # noqa: E731
+    else:
+        rs = list(zip(rets[:3], rets[3:]))
+        f = lambda lev, r, s: (one + lev * np.float32(r)) + (one - lev) * np.float32(s)  # noqa: E731
+    g = lambda lev: np.where(outcomes == 0, f(lev, *rs[0]),  # noqa: E731
+                             np.where(outcomes == 1, f(lev, *rs[1]), f(lev, *rs[2]))).astype(np.float32)
+    return -rets[1] > rets[0], g
+
+
 def dice_smart_lev(outcomes, top, value_0, up_r, down_r, mid_r, lev_low, lev_high, lev_incr):
     """lev/lev_exp.py:586-705 on a [investors, horizon] {0 up, 1 down, 2 mid}
     matrix; factors 1 + lev * r in float32."""
-    levs = _levs(lev_low, lev_high, lev_incr, -down_r > up_r)
-    f = lambda lev, r: np.float32(1) + lev * np.float32(r)  # noqa: E731
-    g = lambda lev: np.where(outcomes == 0, f(lev, up_r), np.where(outcomes == 1, f(lev, down_r),  # noqa: E731
-                                                                    f(lev, mid_r))).astype(np.float32)
-    return sorted_smart_lev(g, levs, top, value_0, outcomes.shape[1])
+    neg, g = _gambles("dice", outcomes, (up_r, down_r, mid_r))
+    return sorted_smart_lev(g, _levs(lev_low, lev_high, lev_incr, neg), top, value_0, outcomes.shape[1])
 
 
 def dice_sh_smart_lev(outcomes, top, value_0, up_r, down_r, mid_r, sh_up_r, sh_down_r, sh_mid_r, lev_low, lev_high,
                       lev_incr):
     """lev/lev_exp.py:1209-1332: factors 1 + lev * r + (1 - lev) * r_sh (float32)."""
-    levs = _levs(lev_low, lev_high, lev_incr, -down_r > up_r)
-    f = lambda lev, r, rs: (np.float32(1) + lev * np.float32(r)) + (np.float32(1) - lev) * np.float32(rs)  # noqa
-    g = lambda lev: np.where(outcomes == 0, f(lev, up_r, sh_up_r),  # noqa: E731
-                             np.where(outcomes == 1, f(lev, down_r, sh_down_r),
-                                      f(lev, mid_r, sh_mid_r))).astype(np.float32)
-    return sorted_smart_lev(g, levs, top, value_0, outcomes.shape[1])
+    neg, g = _gambles("dicesh", outcomes, (up_r, down_r, mid_r, sh_up_r, sh_down_r, sh_mid_r))
+    return sorted_smart_lev(g, _levs(lev_low, lev_high, lev_incr, neg), top, value_0, outcomes.shape[1])
 
 
 def gbm_smart_lev(outcomes, top, value_0, lev_low, lev_high, lev_incr):
     """lev/lev_exp.py:1008-1119: factors exp(lev * outcome) in float32."""
-    levs = _levs(lev_low, lev_high, lev_incr, False)
-    o = outcomes.astype(np.float32)
-    g = lambda lev: np.exp(lev * o).astype(np.float32)  # noqa: E731
-    return sorted_smart_lev(g, levs, top, value_0, outcomes.shape[1])
+    neg, g = _gambles("gbm", outcomes, ())
+    return sorted_smart_lev(g, _levs(lev_low, lev_high, lev_incr, neg), top, value_0, outcomes.shape[1])
+
+
+def final_stats(kind, outcomes, top, value_0, rets, lev_low, lev_high, lev_incr):
+    """The *_fixed_final_lev family (lev/lev_exp.py:56-127 coin, :508-585 dice,
+    :935-1007 gbm, :1121-1208 dicesh): the values after all `horizon` steps
+    (sequential f32 products, horizon 1 included) and their statistics.
+    Returns (stats [n_lev, 13] in the table's row order, values [n_lev, investors])."""
+    neg, g_of_lev = _gambles(kind, outcomes, tuple(rets))
+    levs = _levs(lev_low, lev_high, lev_incr, neg)
+    inv, hor = outcomes.shape
+    stats = np.zeros((len(levs), 13), dtype=np.float32)
+    vals = np.zeros((len(levs), inv), dtype=np.float32)
+    for i, lev in enumerate(levs):
+        g = g_of_lev(lev)
+        val = (np.float32(value_0) * g[:, 0]).astype(np.float32)
+        for t in range(1, hor):
+            val = (val * g[:, t]).astype(np.float32)
+        s = np.sort(val)[::-1]
+        a, tp, ad = _group(val), _group(s[:top]), _group(s[top:])
+        stats[i] = [a[0], tp[0], ad[0], a[1], tp[1], ad[1], a[2], tp[2], ad[2], a[3], tp[3], ad[3], lev]
+        vals[i] = val
+    return stats, vals
 
 
 def brain_lev(codes, rets3, top, value_0, lev_factor, stops, rolls, f64=False):

@@ -30,9 +30,13 @@
 //                        bits match a target's prefix (one per distinct prefix)
 //   sel_scan_kernel      per (array, target): the digit bin holding the target
 //                        rank (wave scan of the histogram), the next prefix
-//   sel_sums_kernel      group sums in f64 (pass 0), then |v - mean| and
-//                        (v - mean)^2 (pass 1); fixed chunk order: deterministic
+//   sel_sums_kernel      |v - mean| and (v - mean)^2 per group in f64; fixed
+//                        chunk order: deterministic
 //   sel_fold_kernel      per array: fold the chunks, write the column
+// Group membership is decided from the KEYS everywhere (-0 and +0 are two keys,
+// as in the tie counts), and each group's sum is formed from that group's values
+// alone: the adjusted group's is never a difference of two larger sums, so a top
+// group that dominates the sum, or holds inf, leaves the adjusted rows exact.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -142,7 +146,8 @@ __device__ __forceinline__ void flush_hist(const unsigned* h, int n, unsigned* g
 
 // pass p >= 1: histogram of digit p over the keys matching a target's prefix
 // On the last pass also the block's sums [all values, values whose key lies
-// above the boundary target's bucket, their count] (part2, fixed order)
+// above the boundary target's bucket, their count, values below that bucket]
+// (part2, fixed order)
 template <typename VT>
 __global__ void __launch_bounds__(kT) sel_hist_kernel(const VT* vals, int64_t N, int p, int last, const SelState* sel,
                                                       unsigned* hist, double* part2) {
@@ -168,7 +173,7 @@ __global__ void __launch_bounds__(kT) sel_hist_kernel(const VT* vals, int64_t N,
   int64_t b0, b1;
   chunk_range(N, blockIdx.x, gridDim.x, b0, b1);
   const K mask = ((K)1 << width) - 1;
-  double sa = 0.0, sab = 0.0, cab = 0.0;
+  double sa = 0.0, sab = 0.0, cab = 0.0, sbl = 0.0;
   for_vals(vals + (int64_t)l * pad4(N), b0, b1, [&](VT x) {
     const K key = okey(x);
     const unsigned d = (unsigned)((key >> shift) & mask);
@@ -182,6 +187,7 @@ __global__ void __launch_bounds__(kT) sel_hist_kernel(const VT* vals, int64_t N,
         sab += (double)x;
         cab += 1.0;
       }
+      if (top_on && hi < pre0) sbl += (double)x;
     }
   });
   __syncthreads();
@@ -189,17 +195,18 @@ __global__ void __launch_bounds__(kT) sel_hist_kernel(const VT* vals, int64_t N,
   for (int q = 0; q < 4; ++q)
     if (on[q]) flush_hist(h + q * kSelBins, kSelBins, hist + ((int64_t)l * 4 + q) * kSelBins);
   if (!last) return;
-  __shared__ double red[3][kT];
+  __shared__ double red[4][kT];
   red[0][threadIdx.x] = sa;
   red[1][threadIdx.x] = sab;
   red[2][threadIdx.x] = cab;
+  red[3][threadIdx.x] = sbl;
   __syncthreads();
   for (int hh = kT / 2; hh > 0; hh >>= 1) {
     if ((int)threadIdx.x < hh)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + hh];
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + hh];
     __syncthreads();
   }
-  if ((int)threadIdx.x < 3) part2[((int64_t)l * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x][0];
+  if ((int)threadIdx.x < 4) part2[((int64_t)l * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // per array (one workgroup, wave q = target q): the bin of digit p that holds
@@ -208,7 +215,9 @@ __global__ void __launch_bounds__(kT) sel_hist_kernel(const VT* vals, int64_t N,
 // On the last pass wave 0 also forms the groups' means from the hist blocks'
 // sums and the boundary bucket's histogram (every bin of the last digit is one
 // value): means[l][0..4] = mean all, top, adjusted, and the boundary value's
-// copies in the top and the adjusted group.
+// copies in the top and the adjusted group.  The top sum is the values above
+// the boundary plus its copies there, the adjusted sum the values below it plus
+// its copies there; empty bins are skipped (beside +-inf their keys are NaNs).
 template <typename VT>
 __global__ void __launch_bounds__(256) sel_scan_kernel(int p, int last, int64_t N, int64_t top, SelState* sel,
                                                        unsigned* hist, const double* part2, double* means) {
@@ -229,7 +238,8 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(int p, int last, int64_t 
     s.src = q;
   }
   unsigned* base = hist + (int64_t)l * 4 * kSelBins;
-  double gsum = 0.0, gcnt = 0.0, ceq = 0.0;  // last pass, wave 0: the boundary bucket above / at the boundary
+  // last pass, wave 0: the boundary bucket's values above (sum, count), at (count) and below (sum) the boundary
+  double gsum = 0.0, gcnt = 0.0, ceq = 0.0, lsum = 0.0;
   if (s.valid) {
     const unsigned* h = base + (p == 0 ? 0 : s.src) * kSelBins;
     unsigned cb[kSelBins / 64];
@@ -270,11 +280,16 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(int p, int last, int64_t 
 #pragma unroll
         for (int j = 0; j < kSelBins / 64; ++j) {
           const int bj = lane * per + j;
-          if (j < per && bj > bin) {
-            gsum += (double)cb[j] * (double)kval((K)((s.prefix << width) | (unsigned long long)bj));
+          if (j >= per || !cb[j]) continue;
+          const double sv = (double)cb[j] * (double)kval((K)((s.prefix << width) | (unsigned long long)bj));
+          if (bj > bin) {
+            gsum += sv;
             gcnt += (double)cb[j];
+          } else if (bj < bin) {
+            lsum += sv;
+          } else {
+            ceq = (double)cb[j];
           }
-          if (j < per && bj == bin) ceq = (double)cb[j];
         }
       }
       s.prefix = (s.prefix << width) | (unsigned long long)bin;
@@ -282,30 +297,35 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(int p, int last, int64_t 
     }
   }
   if (last && q == 0) {
-    double sa = 0.0, sab = gsum, cab = gcnt;
+    double sa = 0.0, sab = gsum, cab = gcnt, sbl = lsum;
     for (int b = lane; b < kSelBlocks; b += 64) {
-      sa += part2[((int64_t)l * kSelBlocks + b) * 3];
-      sab += part2[((int64_t)l * kSelBlocks + b) * 3 + 1];
-      cab += part2[((int64_t)l * kSelBlocks + b) * 3 + 2];
+      sa += part2[((int64_t)l * kSelBlocks + b) * 4];
+      sab += part2[((int64_t)l * kSelBlocks + b) * 4 + 1];
+      cab += part2[((int64_t)l * kSelBlocks + b) * 4 + 2];
+      sbl += part2[((int64_t)l * kSelBlocks + b) * 4 + 3];
     }
     for (int o = 32; o > 0; o >>= 1) {
       sa += __shfl_xor(sa, o, 64);
       sab += __shfl_xor(sab, o, 64);
       cab += __shfl_xor(cab, o, 64);
+      sbl += __shfl_xor(sbl, o, 64);
       ceq += __shfl_xor(ceq, o, 64);
     }
     if (lane == 0) {
       const bool has_top = s.valid != 0;
       const double vk = has_top ? (double)kval((K)s.prefix) : 0.0;
       const double nt = (double)top;
-      const double tie_top = has_top ? nt - cab : 0.0;
+      const double tie_top = has_top ? nt - cab : 0.0;  // >= 1: the boundary element itself
+      const double tie_adj = has_top ? ceq - tie_top : 0.0;
       const double sum_top = has_top ? sab + tie_top * vk : 0.0;
+      // no top group: every value is adjusted; no copy of vk there: no 0 * inf
+      const double sum_adj = has_top ? sbl + (tie_adj > 0.0 ? tie_adj * vk : 0.0) : sa;
       double* m = means + l * 8;
       m[0] = sa / (double)N;
       m[1] = sum_top / nt;
-      m[2] = N > top ? (sa - sum_top) / (double)(N - top) : NAN;
+      m[2] = N > top ? sum_adj / (double)(N - top) : NAN;
       m[3] = tie_top;
-      m[4] = has_top ? ceq - tie_top : 0.0;
+      m[4] = tie_adj;
     }
   }
   __shared__ SelState ss[4];
@@ -324,46 +344,37 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(int p, int last, int64_t 
   }
 }
 
-// group sums over the array's values: pass 0 [sum all, sum v > vk, #(v > vk),
-// #(v == vk)], pass 1 [|v - m_all|, (v - m_all)^2, top |.|, top ^2, adj |.|,
-// adj ^2] (v == vk excluded: the fold adds those copies)
+// deviation sums over the array's values: [|v - m_all|, (v - m_all)^2, top |.|,
+// top ^2, adj |.|, adj ^2]; the top group is key > boundary key, the adjusted
+// key < boundary key (the boundary's copies excluded: the fold adds them)
 template <typename VT>
 __global__ void __launch_bounds__(kT) sel_sums_kernel(const VT* vals, int64_t N, const SelState* sel,
-                                                      const double* means, int pass, double* part) {
+                                                      const double* means, double* part) {
   typedef typename KeyT<VT>::K K;
   const int l = blockIdx.y, c = blockIdx.x;
   const VT* s = vals + (int64_t)l * pad4(N);
   const bool has_top = sel[l * 4].valid != 0;
-  const double vk = has_top ? (double)kval((K)sel[l * 4].prefix) : 0.0;
+  const K kk = (K)sel[l * 4].prefix;
   int64_t b0, b1;
   chunk_range(N, c, kChunks, b0, b1);
   double acc[6] = {0, 0, 0, 0, 0, 0};
-  const double ma = pass ? means[l * 8 + 0] : 0.0, mt = pass ? means[l * 8 + 1] : 0.0,
-               md = pass ? means[l * 8 + 2] : 0.0;
+  const double ma = means[l * 8 + 0], mt = means[l * 8 + 1], md = means[l * 8 + 2];
   for_vals(s, b0, b1, [&](VT x) {
     const double v = (double)x;
-    const bool gt = has_top && v > vk, lt = !has_top || v < vk;
-    if (!pass) {
-      acc[0] += v;
-      if (gt) {
-        acc[1] += v;
-        acc[2] += 1.0;
-      }
-      if (has_top && v == vk) acc[3] += 1.0;
-    } else {
-      const double da = v - ma;
-      acc[0] += fabs(da);
-      acc[1] += da * da;
-      if (gt) {
-        const double d = v - mt;
-        acc[2] += fabs(d);
-        acc[3] += d * d;
-      }
-      if (lt) {
-        const double d = v - md;
-        acc[4] += fabs(d);
-        acc[5] += d * d;
-      }
+    const K key = okey(x);
+    const bool gt = has_top && key > kk, lt = !has_top || key < kk;
+    const double da = v - ma;
+    acc[0] += fabs(da);
+    acc[1] += da * da;
+    if (gt) {
+      const double d = v - mt;
+      acc[2] += fabs(d);
+      acc[3] += d * d;
+    }
+    if (lt) {
+      const double d = v - md;
+      acc[4] += fabs(d);
+      acc[5] += d * d;
     }
   });
   __shared__ double red[6][kT];
@@ -377,13 +388,13 @@ __global__ void __launch_bounds__(kT) sel_sums_kernel(const VT* vals, int64_t N,
   if ((int)threadIdx.x < 6) part[((int64_t)l * kChunks + c) * 6 + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// pass 0: the three groups' means (and the boundary's copies per group); pass 1:
-// the table column at step t.  rows: table rows per array; row0: where the 12
-// statistics go; the n_extra constants extra[l][*] fill rows row0 + 12 ... (the
-// sweeps' lev row, the big-brain stop / roll rows)
+// the table column at step t from the scan's means (and the boundary's copies
+// per group) and the chunks' deviation sums.  rows: table rows per array; row0:
+// where the 12 statistics go; the n_extra constants extra[l][*] fill rows
+// row0 + 12 ... (the sweeps' lev row, the big-brain stop / roll rows)
 template <typename VT>
-__global__ void sel_fold_kernel(int64_t N, int64_t top, int n_arr, const SelState* sel, const double* part, int pass,
-                                double* means, const float* extra, int n_extra, float* data, int rows, int row0,
+__global__ void sel_fold_kernel(int64_t N, int64_t top, int n_arr, const SelState* sel, const double* part,
+                                const double* means, const float* extra, int n_extra, float* data, int rows, int row0,
                                 int steps, int t) {
   typedef typename KeyT<VT>::K K;
   const int l = blockIdx.x;  // one wave per array: lane c folds chunks c, c + 64, ..., then a fixed butterfly
@@ -397,20 +408,10 @@ __global__ void sel_fold_kernel(int64_t N, int64_t top, int n_arr, const SelStat
   const double na = (double)N, nt = (double)top, nd = (double)(N - top);
   const bool has_top = sel[l * 4].valid != 0;
   const double vk = has_top ? (double)kval((K)sel[l * 4].prefix) : 0.0;
-  double* m = means + l * 8;
-  if (!pass) {
-    const double tie_top = has_top ? nt - s[2] : 0.0;  // copies of vk in the top group
-    const double tie_adj = has_top ? s[3] - tie_top : 0.0;
-    const double sum_top = has_top ? s[1] + tie_top * vk : 0.0;
-    m[0] = s[0] / na;
-    m[1] = sum_top / nt;
-    m[2] = N > top ? (s[0] - sum_top) / nd : NAN;
-    m[3] = tie_top;
-    m[4] = tie_adj;
-    return;
-  }
+  const double* m = means + l * 8;
   const double tie_top = m[3], tie_adj = m[4];
-  const double dt = vk - m[1], dd = vk - m[2];
+  // a group without a copy of vk adds nothing (not 0 * inf when vk or a mean is inf)
+  const double dt = tie_top > 0.0 ? vk - m[1] : 0.0, dd = tie_adj > 0.0 ? vk - m[2] : 0.0;
   auto med = [&](int q) -> double {
     const SelState& x = sel[l * 4 + q];
     return x.valid ? (double)kval((K)x.prefix) : NAN;
@@ -435,12 +436,12 @@ struct SelWork {
   unsigned* hist;  // [n_arr][4][kSelBins], zero between passes
   SelState* sel;   // [n_arr][4]
   double* part;    // [n_arr][kChunks][6]
-  double* part2;   // [n_arr][kSelBlocks][3]
+  double* part2;   // [n_arr][kSelBlocks][4]
   double* means;   // [n_arr][8]
 };
 
 size_t sel_work_bytes(int64_t n_arr) {
-  return (size_t)n_arr * (4 * kSelBins * 4 + 4 * sizeof(SelState) + kChunks * 6 * 8 + kSelBlocks * 3 * 8 + 8 * 8) +
+  return (size_t)n_arr * (4 * kSelBins * 4 + 4 * sizeof(SelState) + kChunks * 6 * 8 + kSelBlocks * 4 * 8 + 8 * 8) +
          1024;
 }
 
@@ -450,12 +451,12 @@ SelWork sel_work(unsigned char* p, int64_t n_arr) {
   w.sel = reinterpret_cast<SelState*>(p + n_arr * 4 * kSelBins * 4);
   w.part = reinterpret_cast<double*>(w.sel + n_arr * 4);
   w.part2 = w.part + n_arr * kChunks * 6;
-  w.means = w.part2 + n_arr * kSelBlocks * 3;
+  w.means = w.part2 + n_arr * kSelBlocks * 4;
   return w;
 }
 
 // the column of every array at step t: the select passes (the first digit's
-// histogram already built when hist0_done), then the two sum passes
+// histogram already built when hist0_done), then the deviation sums and the fold
 template <typename VT>
 int sel_stats(const VT* vals, int64_t N, int64_t top, int n_arr, const SelWork& w, bool hist0_done, const float* extra,
               int n_extra, float* data, int rows, int row0, int steps, int t, hipStream_t st) {
@@ -474,9 +475,9 @@ int sel_stats(const VT* vals, int64_t N, int64_t top, int n_arr, const SelWork& 
     RLMD_LAUNCH_CHECK();
   }
   // the deviations from the means, then the column
-  hipLaunchKernelGGL(sel_sums_kernel<VT>, dim3(kChunks, n_arr), dim3(kT), 0, st, vals, N, w.sel, w.means, 1, w.part);
+  hipLaunchKernelGGL(sel_sums_kernel<VT>, dim3(kChunks, n_arr), dim3(kT), 0, st, vals, N, w.sel, w.means, w.part);
   RLMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sel_fold_kernel<VT>, dim3(n_arr), dim3(64), 0, st, N, top, n_arr, w.sel, w.part, 1, w.means,
+  hipLaunchKernelGGL(sel_fold_kernel<VT>, dim3(n_arr), dim3(64), 0, st, N, top, n_arr, w.sel, w.part, w.means,
                      extra, n_extra, data, rows, row0, steps, t);
   RLMD_LAUNCH_CHECK();
   return 0;

@@ -911,6 +911,67 @@ def lev_fixtures(seed=41):
     return out
 
 
+# the sorted sweeps' edge inputs that stay finite (tests/test_lev_edges_gpu.py):
+# name -> (kind, investors, horizon, tops, value_0, returns, lev grid, outcome
+# probabilities (up, down) or None for GBM, all-up rows, seed)
+SH_RETS = (-1.0, 5.0, -1.0)
+LEV_EDGE_CASES = {
+    # N = 1 ... 5: the four select targets share prefixes; empty groups; top clamped
+    **{f"tiny{n}_{kind}": (kind, n, 4, sorted({0, 1, n, n + 5}), 100.0,
+                           {"dice": (0.5, -0.5, 0.05), "dicesh": (0.5, -0.5, 0.05) + SH_RETS, "gbm": ()}[kind],
+                           (0.5, 1.0, 0.5), None if kind == "gbm" else (1 / 3, 1 / 3), (), 50 + n)
+       for n in (1, 2, 3, 4, 5) for kind in ("dice", "dicesh", "gbm")},
+    # factors 3, -0.5, 1.1 at leverage 2 (dicesh 4, -5.5, 2.1): negative values
+    "signed_dice": ("dice", 64, 8, [32], 100.0, (1.0, -0.75, 0.05), (1.0, 2.0, 1.0), (1 / 6, 1 / 6), (), 3),
+    "signed_dicesh": ("dicesh", 64, 8, [32], 100.0, (1.0, -0.75, 0.05) + SH_RETS, (1.0, 2.0, 1.0), (1 / 6, 1 / 6), (),
+                      3),
+    # factors 3, -0.5, 0: zeros of both signs in one tie class
+    "zeros_dice": ("dice", 64, 8, [1, 32, 63], 100.0, (1.0, -0.75, -0.5), (2.0, 2.0, 1.0), (1 / 3, 1 / 3), (), 1),
+    # factors 3, 0.5, 1.1 and three investors that only win: their sum hides the rest
+    "dom_dice": ("dice", 40, 62, [2, 3, 5], 100.0, (1.0, -0.25, 0.05), (2.0, 2.0, 1.0), (1 / 6, 1 / 6), (3, 17, 38),
+                 7),
+}
+
+
+def lev_edge_fixtures():
+    """dice_smart_lev / dice_sh_smart_lev / gbm_smart_lev (lev/lev_exp.py:586,
+    :1209, :1008) of the reference on LEV_EDGE_CASES (torch CPU, float32): per
+    case the outcomes and, per top, the table and the final values."""
+    import contextlib
+    import io
+
+    from lev import lev_exp
+
+    out = {}
+    for name, (kind, inv, hor, tops, v0, rets, grid, probs, all_up, seed) in LEV_EDGE_CASES.items():
+        g = T.Generator().manual_seed(seed)
+        if kind == "gbm":
+            outc = 0.0540025395205692 - 0.1897916175617430 ** 2 / 2 + 0.1897916175617430 * T.randn(
+                (inv, hor), generator=g)
+        else:
+            u = T.rand((inv, hor), generator=g)
+            outc = T.where(u < probs[0], 0.0, T.where(u < probs[0] + probs[1], 1.0, 2.0))
+            for r in all_up:
+                outc[r] = 0.0
+        out[name + "_outcomes"] = outc.numpy().astype(np.float32)
+        out[name + "_args"] = np.array([inv, hor, v0, *grid], dtype=np.float64)
+        out[name + "_rets"] = np.array(rets, dtype=np.float64)
+        out[name + "_tops"] = np.array(tops, dtype=np.int64)
+        for top in tops:
+            with contextlib.redirect_stdout(io.StringIO()):
+                if kind == "gbm":
+                    data, data_T = lev_exp.gbm_smart_lev(T.device("cpu"), outc, inv, hor, top, v0, *grid)
+                elif kind == "dicesh":
+                    data, data_T = lev_exp.dice_sh_smart_lev(T.device("cpu"), outc.numpy(), inv, hor, top, v0, *rets,
+                                                             *grid)
+                else:
+                    data, data_T = lev_exp.dice_smart_lev(T.device("cpu"), outc.numpy(), inv, hor, top, v0, *rets,
+                                                          *grid)
+            out[f"{name}_top{top}_data"] = data.numpy()
+            out[f"{name}_top{top}_data_T"] = data_T.numpy()
+    return out
+
+
 # ----------------------------------------------------------------------------
 # F6: the reference's own C1 loop (scripts/rl_multiplicative.py), recorded
 # ----------------------------------------------------------------------------
@@ -1423,6 +1484,7 @@ def main():
         "env_resources_kat.npz": env_resources_kat,
         "aggregate.npz": aggregate_fixtures,
         "lev_final.npz": lev_final_fixtures,
+        "lev_edges.npz": lev_edge_fixtures,
     }
     only = sys.argv[1:]
     for fn, job in jobs.items():

@@ -86,6 +86,139 @@ def test_galaxy_brain_matches_reference():
     np.testing.assert_array_equal(got, ZF["galaxy"])
 
 
+def close_final(st, ref, rtol):
+    """close_table for one [n_lev, 12] block of final statistics."""
+    means = ref[:, [0, 1, 2] * 4]
+    disp = (np.arange(12) >= 3) & (np.arange(12) < 9)
+    return np.abs(st - ref) <= rtol * np.abs(ref) + rtol * np.abs(means) * disp[None, :] + 1e-30
+
+
+@pytest.mark.parametrize("case", ["coin", "dice", "dicesh", "gbm"])
+def test_final_stats_oracle_matches_reference(case):
+    """oracle final_stats against the statistics the reference's *_fixed_final_lev
+    computed (lev_final.npz): 1e-5 on values and statistics, as the device's test
+    (the reference multiplies with gambles.prod(dim=1), the oracle step by step)."""
+    a, rets = ZF[case + "_args"], [float(x) for x in ZF[case + "_rets"]]
+    st, vals = olev.final_stats(case, ZF[case + "_outcomes"], int(a[2]), a[3], rets, a[4], a[5], a[6])
+    np.testing.assert_allclose(vals, ZF[case + "_values"], rtol=1e-5, atol=0)
+    ok = close_final(st[:, :12], ZF[case + "_stats"], 1e-5)
+    assert ok.all(), np.argwhere(~ok)[:5]
+    np.testing.assert_array_equal(st[:, 12], np.array(olev.param_range(a[4], a[5], a[6]), np.float32))
+
+
+# ---- the sorted sweeps' edge inputs (lev_edges.npz, make_golden.py:lev_edge_fixtures)
+ZE = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lev_edges.npz"))
+EDGES = sorted(k[:-len("_outcomes")] for k in ZE.files if k.endswith("_outcomes"))
+EDGE_TOPS = [(name, int(top)) for name in EDGES for top in ZE[name + "_tops"]]
+
+
+def edge_inputs(name):
+    """(kind, outcomes, value_0, rets, (lev_low, lev_high, lev_incr)) of a lev_edges.npz case."""
+    a = ZE[name + "_args"]
+    return name.split("_")[1], ZE[name + "_outcomes"], a[2], tuple(float(r) for r in ZE[name + "_rets"]), tuple(a[3:6])
+
+
+def edge_oracle(kind, o, top, v0, rets, grid):
+    if kind == "gbm":
+        return olev.gbm_smart_lev(o, top, v0, *grid)
+    if kind == "dicesh":
+        return olev.dice_sh_smart_lev(o, top, v0, *rets, *grid)
+    return olev.dice_smart_lev(o, top, v0, *rets, *grid)
+
+
+def same_finite_and_close(d, ref, rtol, close=close_table):
+    """Finite exactly where the reference is, and there within close(..., rtol)."""
+    fin = np.isfinite(ref)
+    bad = np.isfinite(d) != fin
+    assert not bad.any(), (np.argwhere(bad)[:6], d[bad][:6], ref[bad][:6])
+    ok = close(np.where(fin, d, 0), np.where(fin, ref, 0), rtol)
+    assert ok.all(), (np.argwhere(~ok)[:6], d[~ok][:6], ref[~ok][:6])
+
+
+def lev_paths(kind, o, v0, rets, grid):
+    """The f32 values [n_lev, horizon - 1, investors] behind a sweep's table columns."""
+    neg, g_of_lev = olev._gambles(kind, o, rets)
+    out = []
+    for lev in olev._levs(*grid, neg):
+        g = g_of_lev(lev)
+        v, rows = (np.float32(v0) * g[:, 0]).astype(np.float32), []
+        for t in range(1, o.shape[1]):
+            v = (v * g[:, t]).astype(np.float32)
+            rows.append(v)
+        out.append(rows)
+    return np.array(out)
+
+
+def means_do_not_cancel(table, vals, top, floor=1e-3):
+    """Every finite group mean of `table` (rows 0-2) is at least `floor` of that
+    group's mean |v|: the 2e-6 bound is then a bound on the sums, not on how far
+    a signed group's mean cancels."""
+    for l in range(vals.shape[0]):
+        for t in range(vals.shape[1]):
+            s = np.abs(np.sort(vals[l, t])[::-1].astype(np.float64))
+            for row, grp in enumerate((s, s[:top], s[top:])):
+                m = table[l, row, t]
+                if grp.size and np.isfinite(m) and abs(m) < floor * grp.mean():
+                    return False
+    return True
+
+
+def zero_boundary_steps(vals, top):
+    """Steps of leverage 0 at which the top group's boundary value is zero and
+    the zero class holds both +0 and -0."""
+    n = 0
+    for v in vals[0]:
+        z = v == 0
+        n += bool(np.sort(v)[::-1][top - 1] == 0 and (z & np.signbit(v)).any() and (z & ~np.signbit(v)).any())
+    return n
+
+
+@pytest.mark.parametrize("name,top", EDGE_TOPS)
+def test_sorted_oracle_matches_reference_at_edges(name, top):
+    """The reference's dice / dice_sh / gbm sweeps at 1-5 investors (top 0, 1, N,
+    N + 5: empty groups are NaN rows in both), with negative factors, with a zero
+    factor (zeros of both signs) and with three investors that dominate every
+    sum: values bit-equal (categorical) or 2e-5 (GBM), table 2e-6 / 2e-5."""
+    kind, o, v0, rets, grid = edge_inputs(name)
+    d, dT = edge_oracle(kind, o, top, v0, rets, grid)
+    ref_d, ref_dT = ZE[f"{name}_top{top}_data"], ZE[f"{name}_top{top}_data_T"]
+    assert d.shape == ref_d.shape and dT.shape == ref_dT.shape
+    if kind == "gbm":
+        np.testing.assert_allclose(dT, ref_dT, rtol=2e-5, atol=0)
+        same_finite_and_close(d, ref_d, 2e-5)
+    else:
+        np.testing.assert_array_equal(dT, ref_dT)
+        same_finite_and_close(d, ref_d, 2e-6)
+
+
+@pytest.mark.parametrize("name", ["signed_dice", "signed_dicesh", "zeros_dice"])
+def test_signed_edge_inputs_hold_their_premises(name):
+    """The signed fixtures do hold negative values, no group mean of the oracle or
+    of the reference cancels below 1e-3 of the group's mean |v|, and the
+    signed-zeros matrix puts zeros of both signs in the boundary class."""
+    kind, o, v0, rets, grid = edge_inputs(name)
+    vals = lev_paths(kind, o, v0, rets, grid)
+    assert (vals < 0).any() and (vals > 0).any()
+    for top in ZE[name + "_tops"]:
+        top = int(top)
+        assert means_do_not_cancel(edge_oracle(kind, o, top, v0, rets, grid)[0], vals, top)
+        assert means_do_not_cancel(ZE[f"{name}_top{top}_data"], vals, top)
+    if name == "zeros_dice":
+        assert (vals == 0).any()
+        assert zero_boundary_steps(vals, 32) >= 2
+
+
+def test_dominated_edge_input_is_dominated():
+    """dom_dice: every value finite, and at the last step the three winners' sum
+    exceeds the other 37 investors' by more than 1e16 (the f64 sum of all values
+    does not resolve the adjusted group's)."""
+    kind, o, v0, rets, grid = edge_inputs("dom_dice")
+    vals = lev_paths(kind, o, v0, rets, grid)
+    assert np.isfinite(vals).all()
+    s = np.sort(vals[0, -1].astype(np.float64))
+    assert s[-3:].sum() > 1e16 * s[:-3].sum()
+
+
 BRAIN = ["coinbrain", "dicebrain", "dicebrain0"]
 
 
