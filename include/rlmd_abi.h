@@ -192,6 +192,26 @@ int rlmd_lev_final_sorted(int32_t kind, const void* outcomes_dev, int64_t invest
                           int64_t top, float value_0, const float* table_host, const float* levs_host, int32_t n_lev,
                           void* workspace, int64_t workspace_bytes, float* stats_dev, float* values_dev,
                           void* stream);
+/* Replaces the Bernoulli / Categorical / Normal sampling of lev/coin_flip.py:
+ * 160-161, lev/dice_roll.py:147-148 and lev/gbm.py:123-124: fills the outcome
+ * matrix the sweeps above read, out_dev [investors][ld], on the device.  Draw j
+ * of row i is a pure function of its index: Philox(seed, (first_investor + i,
+ * stream, RLMD_TAG_LEV_OUTCOME, j >> 1)), the (x, y) words for even j and (z, w)
+ * for odd j, so a shard [first_investor, first_investor + investors) of a larger
+ * matrix is that matrix's rows, and oracle/philox.py regenerates every element.
+ * kind 0 (categorical, u8): params_host f64 [5] = {t0, t1, code0, code1, code2}
+ *   with 0 <= t0 <= t1 the cumulative thresholds c0 / cK and c1 / cK and codes in
+ *   0..255; the 53-bit uniform u gives class (t0 <= u) + (t1 <= u) (NumPy's legacy
+ *   choice) and the element is that class's code.  A die (up, down, mid) is
+ *   {p_up, p_up + p_down, 0, 1, 2}; a coin {up_prob, 1, 1, 0, 0} (1 = up).
+ * kind 1 (normal, f32): params_host f64 [2] = {log_mean, vol}; the element is
+ *   (float)(log_mean + vol * z), z the Box-Muller pair of the block (z0 even j,
+ *   z1 odd j), formed in f64 and rounded once.
+ * Every row's ld elements are written: columns horizon .. ld - 1 are 0 (the coin
+ * sweep reads whole 64-step chunks).  ld >= horizon, ld <= 2^30;
+ * first_investor >= 0 and first_investor + investors <= 2^32. */
+int rlmd_lev_outcomes(int32_t kind, uint64_t seed, uint32_t stream, int64_t first_investor, int64_t investors,
+                      int32_t horizon, const double* params_host, void* out_dev, int64_t ld, void* stream_handle);
 
 /* Lane wealth (f64 [N]) and time (i32 [N]) read back for tests/logging. */
 int rlmd_env_lane_state(rlmd_env_t env, double* wealth_host, int32_t* time_host);

@@ -113,7 +113,8 @@ SIGNATURES = {
     "rlmd_lev_final_sorted": (C.c_int, [I32, P, I64, I32, I64, I64, C.c_float, P, P, I32, P, I64, P, P, P]),
     "rlmd_lev_coin_sweep": (C.c_int, [P, I64, I32, I64, I64, C.c_float, C.c_float, C.c_float, P, I32, P, I64, P, P,
                                        P]),
-    "rlmd_eval_market": (C.c_int, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P, P, P]),
+    "rlmd_lev_outcomes": (C.c_int, [I32, U64, C.c_uint32, I64, I64, I32, P, P, I64, P]),
+    "rlmd_eval_market":(C.c_int, [P, P, P, C.c_int64, C.c_int32, C.c_int32, P, P, P, P, P, P, P]),
     "rlmd_profile_enable": (C.c_int, [P, I32]),
     "rlmd_profile_read": (C.c_int, [P, P, P]),
     "rlmd_profile_stride": (C.c_int, [P, I32]),

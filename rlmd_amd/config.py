@@ -279,3 +279,154 @@ def env_tests(gym_envs: Dict[str, list], inputs: dict, load_market=None) -> None
                 "ENV_KEY {}: total time {} period with {} day(s) observed and {} day(s) action spacing must be " \
                 "greater than sample length = {}".format(key, time_length, days, int(inputs["action_days"]),
                                                         sample_length)
+
+
+# ---------------------------------------------------------------------------
+# Leverage experiments: tests/test_input_lev.py coin_flip_tests (:39-165),
+# dice_roll_tests (:168-273), dice_roll_sh_tests (:276-354) and gbm_tests
+# (:357-454), restated for rlmd_amd/lev_experiments.py.  The reference's
+# argument order without its VRAM flag and figure path (the build always runs
+# on the device and does not plot).  One check is added: TOP may not exceed
+# INVESTORS (the reference would index past its sorted values).
+# ---------------------------------------------------------------------------
+_INCR = "increment must by positive"
+_SUBDIR = "file path must be in a sub-directory relative to main.py"
+
+
+def _lev_common(investors, horizon, top, value_0):
+    assert _num(investors), _TFI
+    assert investors > 1
+    assert _num(horizon), _TFI
+    assert horizon > 0
+    assert _num(top), _TFI
+    assert top > 0
+    assert top <= investors, "TOP must not exceed INVESTORS"
+    assert _num(value_0), _TFI
+    assert value_0 > 0
+
+
+def _lev_path(path_results):
+    assert isinstance(path_results, (str, bytes, os.PathLike)), _TS
+    assert path_results[0:2] == "./" and path_results[-1] == "/", _SUBDIR
+
+
+def _lev_grid(low, high, incr):
+    """An investor-1 leverage grid: numbers, a positive increment, low <= high."""
+    for x in (incr, low, high):
+        assert _num(x), _TFI
+    assert incr > 0, _INCR
+    assert low <= high
+
+
+def _unit_grid(low, high, incr):
+    """A stop-loss / retention-ratio grid: floats in [0, 1)."""
+    for x in (incr, low, high):
+        assert isinstance(x, float), _TFI
+    assert incr > 0, _INCR
+    assert 0 <= low <= high < 1
+
+
+def _lev_die(up_prob, down_prob, up_r, down_r, mid_r):
+    assert _num(up_prob), _TFI
+    assert 0 < up_prob < 1
+    assert _num(down_prob), _TFI
+    assert 0 < down_prob < 1
+    assert up_prob + down_prob < 1
+    assert _num(up_r), _TFI
+    assert up_r > 0
+    assert _num(down_r), _TFI
+    assert -1 <= down_r < 0
+    assert _num(mid_r), _TFI
+    assert up_r > mid_r > down_r
+
+
+def _asym(asym_lim):
+    assert isinstance(asym_lim, float), _TFI
+    assert 0 < asym_lim < 1e-3
+
+
+def lev_coin_tests(INVESTORS, HORIZON, TOP, VALUE_0, UP_PROB, UP_R, DOWN_R, ASYM_LIM, path_results, l0_l, l0_h, l0_i,
+                   l1_l, l1_h, l1_i, s2_l, s2_h, s2_i, r2_l, r2_h, r2_i, s3_l, s3_h, s3_i, r3_l, r3_h, r3_i, ru_l, ru_h,
+                   ru_i, rd_l, rd_h, rd_i, pu_l, pu_h, pu_i) -> None:
+    """tests/test_input_lev.py:39-165 (lev/coin_flip.py's inputs)."""
+    _lev_common(INVESTORS, HORIZON, TOP, VALUE_0)
+    assert _num(UP_PROB), _TFI
+    assert 0 < UP_PROB < 1
+    assert _num(UP_R), _TFI
+    assert UP_R > 0
+    assert _num(DOWN_R), _TFI
+    assert -1 <= DOWN_R < 0
+    _asym(ASYM_LIM)
+    _lev_path(path_results)
+    _lev_grid(l0_l, l0_h, l0_i)
+    _lev_grid(l1_l, l1_h, l1_i)
+    _unit_grid(s2_l, s2_h, s2_i)
+    _unit_grid(r2_l, r2_h, r2_i)
+    _unit_grid(s3_l, s3_h, s3_i)
+    _unit_grid(r3_l, r3_h, r3_i)
+    for low, high, incr in ((ru_l, ru_h, ru_i), (rd_l, rd_h, rd_i)):
+        for x in (incr, low, high):
+            assert _num(x), _TFI
+        assert incr > 0, _INCR
+        assert 0 < low <= high
+    for x in (pu_i, pu_l, pu_h):
+        assert isinstance(x, float), _TF
+    assert pu_i > 0, _INCR
+    assert 0 < pu_l <= pu_h < 1
+    assert int(pu_h / pu_i + 1) - int(pu_l / pu_i) == 3, "3 unique probability increments are required"
+
+
+def lev_dice_tests(INVESTORS, HORIZON, TOP, VALUE_0, UP_PROB, DOWN_PROB, UP_R, DOWN_R, MID_R, ASYM_LIM, path_results,
+                   l0_l, l0_h, l0_i, l1_l, l1_h, l1_i, s2_l, s2_h, s2_i, r2_l, r2_h, r2_i, s3_l, s3_h, s3_i, r3_l,
+                   r3_h, r3_i) -> None:
+    """tests/test_input_lev.py:168-273 (lev/dice_roll.py's inputs)."""
+    _lev_common(INVESTORS, HORIZON, TOP, VALUE_0)
+    _lev_die(UP_PROB, DOWN_PROB, UP_R, DOWN_R, MID_R)
+    _asym(ASYM_LIM)
+    _lev_path(path_results)
+    _lev_grid(l0_l, l0_h, l0_i)
+    _lev_grid(l1_l, l1_h, l1_i)
+    _unit_grid(s2_l, s2_h, s2_i)
+    _unit_grid(r2_l, r2_h, r2_i)
+    _unit_grid(s3_l, s3_h, s3_i)
+    _unit_grid(r3_l, r3_h, r3_i)
+
+
+def lev_dice_sh_tests(INVESTORS, HORIZON, TOP, VALUE_0, UP_PROB, DOWN_PROB, UP_R, DOWN_R, MID_R, SH_UP_R, SH_DOWN_R,
+                      SH_MID_R, path_results, l0_l, l0_h, l0_i, l1_l, l1_h, l1_i) -> None:
+    """tests/test_input_lev.py:276-354 (lev/dice_roll_sh.py's inputs)."""
+    _lev_common(INVESTORS, HORIZON, TOP, VALUE_0)
+    _lev_die(UP_PROB, DOWN_PROB, UP_R, DOWN_R, MID_R)
+    assert _num(SH_UP_R), _TFI
+    assert -1 <= SH_UP_R < 0
+    assert _num(SH_DOWN_R), _TFI
+    assert SH_DOWN_R > 0
+    assert _num(SH_MID_R), _TFI
+    assert -1 <= SH_MID_R < SH_DOWN_R
+    assert SH_MID_R >= SH_UP_R
+    _lev_path(path_results)
+    _lev_grid(l0_l, l0_h, l0_i)
+    _lev_grid(l1_l, l1_h, l1_i)
+
+
+def lev_gbm_tests(INVESTORS, HORIZON, TOP, VALUE_0, drift, vol, name, path_results, l0_l, l0_h, l0_i, l1_l, l1_h,
+                  l1_i, log=print) -> None:
+    """tests/test_input_lev.py:357-454 (lev/gbm.py's inputs: one entry per environment)."""
+    _lev_common(INVESTORS, HORIZON, TOP, VALUE_0)
+    _lev_path(path_results)
+    lists = (drift, vol, name, l0_i, l0_l, l0_h, l1_i, l1_l, l1_h)
+    for x in lists:
+        assert isinstance(x, list), _TL
+    assert len(name) == len(set(name)), "must contain only unique elements"
+    assert len({len(x) for x in lists}) == 1, "all input lists must be of equal length"
+    assert len(drift) > 0, "must contain at least one environment"
+    for x in range(len(drift)):
+        assert _num(drift[x]), _TFI
+        assert _num(vol[x]), _TFI
+        assert vol[x] > 0, "volatility {} must be non-zero and non-negative".format(vol[x])
+        assert isinstance(name[x], str), _TS
+        if drift[x] < vol[x] ** 2 / 2:
+            log("Optimal leverage for situations where u < s^2 / 2 (u={}, s={}) are not stable.".format(drift[x],
+                                                                                                        vol[x]))
+        _lev_grid(l0_l[x], l0_h[x], l0_i[x])
+        _lev_grid(l1_l[x], l1_h[x], l1_i[x])

@@ -21,6 +21,7 @@
 #define RLMD_TAG_TD3_TARGET 7u     // TD3 target policy smoothing noise
 #define RLMD_TAG_MKT_START 8u      // market episode start index (c0 = lane, c1 = episode)
 #define RLMD_TAG_MKT_PERM 9u       // market in-block shuffles (c0 = lane, c1 = episode, c3 = block)
+#define RLMD_TAG_LEV_OUTCOME 10u   // leverage outcome matrices (c0 = investor, c1 = stream, c3 = step pair)
 
 struct rlmd_u32x4 {
   uint32_t x, y, z, w;

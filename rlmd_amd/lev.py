@@ -37,6 +37,59 @@ def pack_outcomes(outcomes, device="cuda:0"):
     return buf, hor
 
 
+def sample_outcomes(kind, investors, horizon, seed=420, stream=0, first_investor=0, device="cuda:0", *, up_prob=0.5,
+                    probs=(1 / 6, 1 / 6, 2 / 3), log_mean=0.0, vol=1.0):
+    """The outcome matrix of one experiment, drawn on the device (rlmd_lev_outcomes,
+    lev_gen.hip) in the form the sweeps read, replacing lev/coin_flip.py:160-161
+    (Bernoulli), lev/dice_roll.py:147-148 (Categorical) and lev/gbm.py:123-124 (Normal):
+      "coin"  the (buf, horizon) pair of pack_outcomes, u8 rows padded to 64 steps,
+              1 = up (u < up_prob), pad 0;
+      "dice"  u8 [investors, horizon] in {0 up, 1 down, 2 mid} for probs (up, down, mid),
+              NumPy's legacy choice on the f64 cumulative thresholds;
+      "gbm"   f32 [investors, horizon], (float)(log_mean + vol * z).
+    Draw j of investor i is Philox(seed, first_investor + i, stream, tag 10, j >> 1):
+    rows [a, b) drawn with first_investor=a are rows a..b-1 of the whole matrix, and
+    oracle.philox.uniform_draws / normal_draws regenerate it on the CPU."""
+    dev = torch.device(device)
+    inv, hor = int(investors), int(horizon)
+    if kind == "coin":
+        ld = (hor + 63) // 64 * 64
+        params = [float(up_prob), 1.0, 1.0, 0.0, 0.0]  # class 0 (u < up_prob) -> code 1 up, class 1 -> 0 down
+    elif kind == "dice":
+        ld = hor
+        c = np.cumsum(np.asarray(probs, dtype=np.float64))
+        if c.shape != (3,):
+            raise ValueError("probs must be the three probabilities (up, down, mid)")
+        params = [c[0] / c[2], c[1] / c[2], 0.0, 1.0, 2.0]
+    elif kind == "gbm":
+        ld = hor
+        params = [float(log_mean), float(vol)]
+    else:
+        raise ValueError("kind must be 'coin', 'dice' or 'gbm'")
+    out = torch.empty((max(inv, 0), max(ld, 0)), dtype=torch.float32 if kind == "gbm" else torch.uint8, device=dev)
+    par = np.ascontiguousarray(params, dtype=np.float64)
+    with torch.cuda.device(dev):
+        _abi.check(_abi.lib().rlmd_lev_outcomes(1 if kind == "gbm" else 0, int(seed), int(stream), int(first_investor),
+                                                inv, hor, par.ctypes.data, _abi.ptr(out), ld, _abi.stream_ptr()))
+    return (out, hor) if kind == "coin" else out
+
+
+def _pair_codes(outcomes, dev):
+    """coin outcomes as (u8 device rows, investors, horizon): a (buf, horizon) pair of
+    pack_outcomes / sample_outcomes is passed through with its row stride (no copy),
+    any other matrix converted (o == 1) as before."""
+    if isinstance(outcomes, tuple):
+        buf, hor = outcomes
+        if buf.dtype != torch.uint8 or buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[1] < int(hor):
+            raise ValueError("an outcome pair is (u8 [investors, ld >= horizon] with unit column stride, horizon)")
+        if buf.device.type != dev.type or (dev.index is not None and buf.device.index != dev.index):
+            raise ValueError("the outcome pair's buffer must be on the sweep's device")
+        return buf, buf.shape[0], int(hor)
+    o = torch.as_tensor(outcomes)
+    inv, hor = o.shape
+    return (o == 1).to(device=dev, dtype=torch.uint8).contiguous(), inv, hor
+
+
 def coin_smart_lev(device, outcomes, investors, horizon, top, value_0, up_r, down_r, lev_low, lev_high, lev_incr,
                    final_values=True):
     """lev_exp.py:128-237 on the device; outcomes may be a torch / NumPy 0/1
@@ -57,6 +110,12 @@ def coin_smart_lev(device, outcomes, investors, horizon, top, value_0, up_r, dow
                                        float(down_r), levs.ctypes.data, n_lev, P(ws), ws.numel(), P(data),
                                        P(data_T) if data_T is not None else None, _abi.stream_ptr()))
     return data, data_T
+
+
+def _view_ptr(t):
+    """Device pointer of an outcome matrix whose rows may be strided (ld = t.stride(0))."""
+    assert t.stride(1) == 1, "outcome rows must have unit column stride"
+    return _abi.C.c_void_p(t.data_ptr())
 
 
 def _lev_range(lev_low, lev_high, lev_incr, negate):
@@ -147,30 +206,30 @@ def _final(kind, dev, outc, inv, hor, top, value_0, table, levs, verbose):
     lv = np.ascontiguousarray(levs.numpy(), dtype=np.float32)
     tb = None if table is None else np.ascontiguousarray(table, dtype=np.float32)
     P = _abi.ptr
-    _abi.check(lib.rlmd_lev_final_sorted(kind, P(outc), int(inv), int(hor), outc.stride(0), int(top), float(value_0),
-                                         None if tb is None else tb.ctypes.data, lv.ctypes.data, n_lev, P(ws),
-                                         ws.numel(), P(stats), P(values), _abi.stream_ptr()))
-    if verbose:  # the reference's summary lines (lev_exp.py:103-125)
+    _abi.check(lib.rlmd_lev_final_sorted(kind, _view_ptr(outc), int(inv), int(hor), outc.stride(0), int(top),
+                                         float(value_0), None if tb is None else tb.ctypes.data, lv.ctypes.data, n_lev,
+                                         P(ws), ws.numel(), P(stats), P(values), _abi.stream_ptr()))
+    if verbose:  # the reference's summary lines (lev_exp.py:103-125); a callable receives them instead of print
+        emit = verbose if callable(verbose) else print
         for row in stats.cpu().numpy():
             m, mt, ma, d, dt, da, s, st, sa, md, mdt, mda, lev = row
-            print(f"       lev {lev * 100:1.0f}%:\n"
-                  f"                 avg mean/med/mad/std:  $ {m:1.2e} / {md:1.2e} / {d:1.1e} / {s:1.1e}\n"
-                  f"                 top mean/med/mad/std:  $ {mt:1.2e} / {mdt:1.2e} / {dt:1.1e} / {st:1.1e}\n"
-                  f"                 adj mean/med/mad/std:  $ {ma:1.2e} / {mda:1.2e} / {da:1.1e} / {sa:1.1e}")
+            emit(f"       lev {lev * 100:1.0f}%:\n"
+                 f"                 avg mean/med/mad/std:  $ {m:1.2e} / {md:1.2e} / {d:1.1e} / {s:1.1e}\n"
+                 f"                 top mean/med/mad/std:  $ {mt:1.2e} / {mdt:1.2e} / {dt:1.1e} / {st:1.1e}\n"
+                 f"                 adj mean/med/mad/std:  $ {ma:1.2e} / {mda:1.2e} / {da:1.1e} / {sa:1.1e}")
     return stats, values
 
 
 def coin_fixed_final_lev(device, outcomes, top, value_0, up_r, down_r, lev_low, lev_high, lev_incr, verbose=False):
     """lev/lev_exp.py:56-127: statistics of value_0 * prod(1 + lev * r) per leverage
     (outcome 1 up, else down).  Returns (stats [n_lev, 13] in STAT_NAMES order,
-    final values [n_lev, investors]); the reference prints the statistics only."""
+    final values [n_lev, investors]); the reference prints the statistics only.
+    outcomes: a 0/1 matrix, or a (u8 device buffer, horizon) pair read in place."""
     dev = torch.device(device)
     up_r, down_r = float(up_r), float(down_r)
     levs = _lev_range(lev_low, lev_high, lev_incr, -down_r > up_r)
     table = torch.stack([torch.stack([1 + lev * down_r, 1 + lev * up_r, 1 + lev * up_r]) for lev in levs])
-    o = torch.as_tensor(outcomes)
-    inv, hor = o.shape
-    outc = (o == 1).to(device=dev, dtype=torch.uint8).contiguous()
+    outc, inv, hor = _pair_codes(outcomes, dev)
     return _final(0, dev, outc, inv, hor, top, value_0, table.numpy(), levs, verbose)
 
 
@@ -217,12 +276,16 @@ def coin_galaxy_brain_lev(device, ru_min, ru_max, ru_incr, rd_min, rd_max, rd_in
     ru_range = param_range(ru_min, ru_max, ru_incr)
     rd_range = param_range(rd_min, rd_max, rd_incr)
     pu_range = param_range(pu_min, pu_max, pu_incr)
-    data = torch.zeros((len(pu_range), len(ru_range), len(ru_range), 4))
-    for i, pu in enumerate(pu_range):
-        for j, ru in enumerate(ru_range):
-            for k, rd in enumerate(rd_range):
-                data[i, j, k, :] = torch.tensor([pu, ru, rd, pu / rd - (1 - pu) / ru])
-    return data.to(torch.device(device))
+    if len(rd_range) > len(ru_range):
+        raise IndexError("rd's grid is longer than ru's, which sizes the third axis")
+    # the same f64 operations per element as the reference's loop, over the whole grid at once
+    # (the experiment's 3 x 601 x 601 grid is a million Python iterations otherwise)
+    pu = np.array(pu_range, dtype=np.float64).reshape(-1, 1, 1)
+    ru = np.array(ru_range, dtype=np.float64).reshape(1, -1, 1)
+    rd = np.array(rd_range, dtype=np.float64).reshape(1, 1, -1)
+    data = np.zeros((len(pu_range), len(ru_range), len(ru_range), 4), dtype=np.float32)
+    data[:, :, :len(rd_range), :] = np.stack(np.broadcast_arrays(pu, ru, rd, pu / rd - (1 - pu) / ru), axis=-1)
+    return torch.from_numpy(data).to(torch.device(device))
 
 
 # ---------------------------------------------------------------------------
@@ -248,9 +311,9 @@ def _brain(device, codes, inv, hor, top, value_0, rets3, lev_factor, stops, roll
     # coin: T.where(outcomes == 1, up_r, down_r) is f32; dice's outcomes are f64
     r3 = np.ascontiguousarray([float(r) if f64 else float(np.float32(r)) for r in rets3], dtype=np.float64)
     P = _abi.ptr
-    _abi.check(lib.rlmd_lev_brain(1 if f64 else 0, P(codes), int(inv), int(hor), codes.stride(0), int(top), float(value_0),
-                                  r3.ctypes.data, float(lf), cfg.ctypes.data, n_cfg, P(ws), ws.numel(), P(data),
-                                  _abi.stream_ptr()))
+    _abi.check(lib.rlmd_lev_brain(1 if f64 else 0, _view_ptr(codes), int(inv), int(hor), codes.stride(0), int(top),
+                                  float(value_0), r3.ctypes.data, float(lf), cfg.ctypes.data, n_cfg, P(ws), ws.numel(),
+                                  P(data), _abi.stream_ptr()))
     return data
 
 
@@ -262,12 +325,14 @@ def coin_big_brain_lev(device, outcomes, investors, horizon, top, value_0, up_r,
     retention ratio > 0 the reference's coin_optimal_lev is handed the Python
     float value_0 for the first leverage and torch.where rejects its bool
     condition (TypeError); the build applies dice_optimal_lev's reading (the
-    floor at value_0 is the stop-loss), which the reference uses for dice."""
+    floor at value_0 is the stop-loss), which the reference uses for dice.
+    outcomes: a 0/1 matrix, or a (u8 device buffer, horizon) pair read in place."""
     dev = torch.device(device)
     stops = torch.tensor(param_range(stop_min, stop_max, stop_incr), dtype=torch.float32)
     rolls = torch.tensor(param_range(roll_min, roll_max, roll_incr), dtype=torch.float32)
-    o = torch.as_tensor(outcomes)
-    codes = (o == 1).to(device=dev, dtype=torch.uint8).contiguous()  # code 0 down, 1 up
+    codes, inv, hor = _pair_codes(outcomes, dev)  # code 0 down, 1 up
+    if isinstance(outcomes, tuple) and (inv != int(investors) or hor != int(horizon)):
+        raise ValueError("outcomes shape does not match investors x horizon")
     return _brain(dev, codes, int(investors), int(horizon), top, value_0, [float(down_r), float(up_r), float(up_r)],
                   lev_factor, stops, rolls, False)
 

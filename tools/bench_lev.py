@@ -3,7 +3,11 @@ coin_smart_lev over 1e6 investors x 3e3 steps x 10 leverages (0.1..1.0), on one
 MI355X.  Prints one JSON line: investor-steps-leverages per second over the
 whole sweep (outcomes resident in HBM), each kernel's HIP-event time, and the
 oracle (the reference's sort-per-step algorithm restated in NumPy) timed on a
-bounded sample on the host cores."""
+bounded sample on the host cores.  --outcomes picks where the outcome matrix is
+drawn: torch (torch.rand / torch.randn in slabs, compared and narrowed) or device
+(lev.sample_outcomes, rlmd_lev_outcomes); either way its HIP-event time is
+reported as outcomes_ms (and outcomes_repeat_ms: the same draw again into the
+freed block), apart from the sweeps."""
 import argparse
 import json
 import os
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kind", default="coin", choices=["coin", "dice", "dice_sh", "gbm", "coin_flip"])
+    ap.add_argument("--outcomes", default="torch", choices=["torch", "device"])
     a = ap.parse_args()
     if a.kind == "coin_flip":
         return coin_flip_main(a)
@@ -31,13 +36,7 @@ def main():
         return sorted_main(a)
     dev = torch.device("cuda:0")
     inv, hor = a.investors, a.horizon
-    g = torch.Generator(device=dev).manual_seed(420)
-    ld = (hor + 63) // 64 * 64
-    buf = torch.zeros((inv, ld), dtype=torch.uint8, device=dev)
-    step = 1 << 17
-    for i in range(0, inv, step):  # Bernoulli(0.5) outcomes, generated in slabs
-        n = min(step, inv - i)
-        buf[i:i + n, :hor] = (torch.rand((n, hor), generator=g, device=dev) < 0.5).to(torch.uint8)
+    buf, outcomes_ms = timed_outcomes(a, dev, lambda: coin_outcomes(a, dev, padded=True))
     top = int(inv * 1e-4)
     args = (inv, hor, top, 100.0, 0.5, -0.4, 0.1, 1.0, 0.1)
     lev.coin_smart_lev(dev, (buf, hor), *args)  # warm-up
@@ -53,7 +52,8 @@ def main():
     units = inv * hor * n_lev
     out = {"metric": "coin_smart_lev investor-steps-leverages/s", "value": units / (ms / 1e3), "unit": "1/s",
            "ms_per_sweep": ms, "config": {"investors": inv, "horizon": hor, "n_lev": n_lev, "top": top},
-           "outcome_bytes": inv * ld, "finite_rows": int(torch.isfinite(data).all(dim=(1, 2)).sum())}
+           "outcome_bytes": inv * buf.shape[1], "outcomes": a.outcomes, **outcomes_ms,
+           "finite_rows": int(torch.isfinite(data).all(dim=(1, 2)).sum())}
     if not a.no_cpu_baseline:
         from oracle import lev as olev
 
@@ -66,19 +66,64 @@ def main():
     print(json.dumps(out))
 
 
+def coin_outcomes(a, dev, padded):
+    """Bernoulli(0.5) outcomes as u8: rows padded to 64 steps (the coin sweep's
+    buffer) or plain [investors, horizon]; torch draws them in slabs."""
+    inv, hor = a.investors, a.horizon
+    if a.outcomes == "device":
+        buf, _ = lev.sample_outcomes("coin", inv, hor, seed=420, device=dev, up_prob=0.5)
+        return buf
+    g = torch.Generator(device=dev).manual_seed(420)
+    ld = (hor + 63) // 64 * 64 if padded else hor
+    buf = (torch.zeros if padded else torch.empty)((inv, ld), dtype=torch.uint8, device=dev)
+    step = 1 << 17
+    for i in range(0, inv, step):
+        n = min(step, inv - i)
+        buf[i:i + n, :hor] = (torch.rand((n, hor), generator=g, device=dev) < 0.5).to(torch.uint8)
+    return buf
+
+
+def timed_outcomes(a, dev, make):
+    """(outcomes, {outcomes_ms, outcomes_repeat_ms}): the HIP-event time of drawing
+    them, and of drawing them again once the first matrix is freed (the allocator
+    then holds its block, so the repeat has no device allocation in it).  Both
+    generators run once at a small size first, so neither holds a first launch."""
+    torch.rand((64, 64), device=dev), torch.randn((64, 64), device=dev)
+    lev.sample_outcomes("gbm" if a.kind == "gbm" else "dice", 64, 64, device=dev)
+    ms = []
+    o = None
+    for _ in range(2):
+        del o
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        o = make()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return o, {"outcomes_ms": ms[0], "outcomes_repeat_ms": ms[1]}
+
+
 def sorted_main(a):
     """dice_smart_lev / dice_sh_smart_lev / gbm_smart_lev (rlmd_lev_sweep_sorted:
     a device radix sort per (step, leverage)) at the given size, 10 leverages
     (lev/dice_roll.py, dice_roll_sh.py, gbm.py grids 0.1..1.0)."""
     dev = torch.device("cuda:0")
     inv, hor = a.investors, a.horizon
-    g = torch.Generator(device=dev).manual_seed(420)
-    if a.kind == "gbm":
-        o = (0.0540025395205692 - 0.1897916175617430 ** 2 / 2
-             + 0.1897916175617430 * torch.randn((inv, hor), generator=g, device=dev))
-    else:
+    def make():
+        if a.outcomes == "device":
+            if a.kind == "gbm":
+                return lev.sample_outcomes("gbm", inv, hor, seed=420, device=dev, vol=0.1897916175617430,
+                                           log_mean=0.0540025395205692 - 0.1897916175617430 ** 2 / 2)
+            return lev.sample_outcomes("dice", inv, hor, seed=420, device=dev)
+        g = torch.Generator(device=dev).manual_seed(420)
+        if a.kind == "gbm":
+            return (0.0540025395205692 - 0.1897916175617430 ** 2 / 2
+                    + 0.1897916175617430 * torch.randn((inv, hor), generator=g, device=dev))
         u = torch.rand((inv, hor), generator=g, device=dev)
-        o = torch.where(u < 1 / 6, 0.0, torch.where(u < 2 / 6, 1.0, 2.0))
+        return torch.where(u < 1 / 6, 0.0, torch.where(u < 2 / 6, 1.0, 2.0))
+
+    o, outcomes_ms = timed_outcomes(a, dev, make)
     top = int(inv * 1e-4)
     if a.kind == "dice":
         run = lambda: lev.dice_smart_lev(dev, o, inv, hor, top, 100.0, 0.5, -0.5, 0.05, 0.1, 1.0, 0.1)  # noqa
@@ -98,7 +143,8 @@ def sorted_main(a):
     ms = e0.elapsed_time(e1) / a.reps
     n_lev = data.shape[0]
     out = {"metric": f"{a.kind}_smart_lev investor-steps-leverages/s", "value": inv * hor * n_lev / (ms / 1e3),
-           "unit": "1/s", "ms_per_sweep": ms, "ms_per_step": ms / (hor - 1),
+           "unit": "1/s", "ms_per_sweep": ms, "ms_per_step": ms / (hor - 1), "outcomes": a.outcomes,
+           **outcomes_ms,
            "config": {"investors": inv, "horizon": hor, "n_lev": n_lev, "top": top}}
     if not a.no_cpu_baseline:
         from oracle import lev as olev
@@ -127,12 +173,9 @@ def coin_flip_main(a):
     call timed with events; one JSON line."""
     dev = torch.device("cuda:0")
     inv, hor = a.investors, a.horizon
-    g = torch.Generator(device=dev).manual_seed(420)
-    o = torch.empty((inv, hor), dtype=torch.uint8, device=dev)
-    step = 1 << 17
-    for i in range(0, inv, step):
-        n = min(step, inv - i)
-        o[i:i + n] = (torch.rand((n, hor), generator=g, device=dev) < 0.5).to(torch.uint8)
+    o, outcomes_ms = timed_outcomes(a, dev, lambda: coin_outcomes(a, dev, padded=False))
+    if a.outcomes == "device":
+        o = (o, hor)  # the pair every coin call reads in place
     top = int(inv * 1e-4)
     calls = {
         "coin_fixed_final_lev (20 levs)": lambda: lev.coin_fixed_final_lev(dev, o, top, 100.0, 0.5, -0.4, 0.05, 1.0,
@@ -144,7 +187,8 @@ def coin_flip_main(a):
                                                                              2.5, 0.05, 0.95, 0.05, 0.7, 0.95, 0.05),
     }
     out = {"metric": "lev/coin_flip.py experiment wall time on one MI355X", "unit": "s",
-           "config": {"investors": inv, "horizon": hor, "top": top}, "calls_ms": {}}
+           "config": {"investors": inv, "horizon": hor, "top": top}, "outcomes": a.outcomes,
+           **outcomes_ms, "calls_ms": {}}
     total = 0.0
     for name, fn in calls.items():
         torch.cuda.synchronize()
