@@ -56,7 +56,12 @@ typedef struct {
   int32_t shuffle_days;/* market: in-block shuffle interval (train 5, eval 3) */
   int32_t sample_days; /* market: days excluded from the start draw (rl_market.py:59) */
   int32_t slice_groups;/* market: lanes l, l' with l % G == l' % G draw the same episode
-                          slices and shuffles (0 = every lane its own; a probe switch) */
+                          slices and shuffles: the start row and the block permutations
+                          are keyed on l % G and the lane's own episode index, so two
+                          lanes of a group share a slice while at the same episode index.
+                          G = 1 is C4's configured data regime (one time_slice +
+                          shuffle_data per episode, rl_market.py:202-214); <= 0 = every
+                          lane its own stream */
   uint64_t seed;       /* Philox key for env draws */
 } rlmd_env_cfg;
 

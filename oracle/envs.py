@@ -120,9 +120,20 @@ class OracleVecEnv:
     """N independent reference envs of one class, stepped in lock-step."""
 
     def __init__(self, family, investor, n_lanes, n_gambles=1, seed=0, prices=None,
-                 obs_days=1, time_length=0, action_days=1, shuffle_days=1, sample_days=0):
+                 obs_days=1, time_length=0, action_days=1, shuffle_days=1, sample_days=0, slice_groups=0):
+        """slice_groups (market): G > 0 makes lanes l, l' with l % G == l' % G share
+        their episode slices, the vectorised form of the reference's loop, which
+        draws one time_slice + shuffle_data per episode for everything trained on
+        it (scripts/rl_market.py:202-214, tools/env_resources.py:229-291): the
+        Philox counter word of the start draw and of the block permutations is
+        lane % G instead of the lane.  The episode index stays the lane's own, so
+        two lanes of a group share a slice only while they are at the same episode
+        index.  G <= 0: every lane its own stream (env.hip clamps it the same way).
+        start_at resets and the other families ignore it."""
         self.f, self.inv, self.N, self.n = family, investor, n_lanes, n_gambles
         self.seed = seed
+        self.slice_groups = max(int(slice_groups), 0)
+        self._rowmaps = {}  # (slice key, episode, start) -> row map, shared by a group's lanes
         self.obs_days, self.time_length = max(obs_days, 1), time_length
         self.action_days, self.shuffle_days = max(action_days, 1), max(shuffle_days, 1)
         self.S, self.A, self.R, self.D = dims(family, investor, n_gambles, self.obs_days)
@@ -139,15 +150,25 @@ class OracleVecEnv:
         self.reset()
 
     # -- market helpers -----------------------------------------------------
+    def slice_key(self, lane):
+        """The Philox counter word of a lane's slice draws (start row, block shuffles)."""
+        return int(lane) % self.slice_groups if self.slice_groups > 0 else int(lane)
+
     def _episode_rows(self, lane):
-        ep = int(self.episode[lane])
-        L, D = self.ext_len, self.shuffle_days
-        full = L // D
-        perms = []
-        for b in range(full + (1 if L % D else 0)):
-            bs = D if b < full else L - full * D
-            perms.append(block_perm(self.seed, lane, ep, b, bs) if D > 1 else [0])
-        return int(self.start[lane]) + shuffle_rows(L, D, perms)
+        key, ep, start = self.slice_key(lane), int(self.episode[lane]), int(self.start[lane])
+        rows = self._rowmaps.get((key, ep, start))
+        if rows is None:
+            L, D = self.ext_len, self.shuffle_days
+            full = L // D
+            perms = []
+            for b in range(full + (1 if L % D else 0)):
+                bs = D if b < full else L - full * D
+                perms.append(block_perm(self.seed, key, ep, b, bs) if D > 1 else [0])
+            rows = start + shuffle_rows(L, D, perms)
+            rows.setflags(write=False)
+            if self.slice_groups > 0:  # per-lane keys are never asked for twice
+                self._rowmaps[(key, ep, start)] = rows
+        return rows
 
     def market_obs(self, lane, t):
         rows, assets = observed_rows(t, self.action_days, self.obs_days, self.n)
@@ -167,7 +188,7 @@ class OracleVecEnv:
             st = np.zeros(self.S)
             st[0:4] = [INITIAL_VALUE, 0, 1, 1]
             if self.f == MARKET:
-                v = px.philox(self.seed, lane, int(self.episode[lane]), px.TAG_MKT_START, 0)
+                v = px.philox(self.seed, self.slice_key(lane), int(self.episode[lane]), px.TAG_MKT_START, 0)
                 self.start[lane] = (int(px.below(v[0], v[1], self.start_range)) if start_at is None
                                     else int(start_at[lane]))
                 self.rowmap[lane] = self._episode_rows(lane)

@@ -78,8 +78,13 @@ class VecEnv:
 
     def __init__(self, family, investor, n_lanes, n_gambles=1, seed=0, prices=None, obs_days=1,
                  time_length=0, action_days=1, shuffle_days=1, sample_days=0, device="cuda:0", slice_groups=0):
-        """slice_groups (market, a probe switch): lanes l and l' with l % G == l' % G
-        draw the same episode slices and block shuffles; 0 = every lane its own."""
+        """slice_groups (market): lanes l and l' with l % G == l' % G draw the same
+        episode slices and block shuffles.  The start row and the shuffles are keyed
+        on l % G, the episode index stays the lane's own: a lane that ends early
+        moves on to its group's next slice while its group mates finish the old
+        one.  G = 1 is C4's configured data regime, the reference's one time_slice +
+        shuffle_data per episode (rl_market.py:202-214) vectorised over the lanes'
+        policy noise; G <= 0 = every lane its own stream."""
         self.family = FAMILY[family] if isinstance(family, str) else family
         self.investor = INVESTOR[investor] if isinstance(investor, str) else investor
         self.n_lanes, self.n_gambles, self.device = n_lanes, n_gambles, torch.device(device)

@@ -123,3 +123,91 @@ def test_market_shuffled_lanes_match_oracle(golden, dev, inv, d):
         if mask.any():
             s_gpu = env.reset(torch.from_numpy(mask).to(dev)).cpu().numpy()
             np.testing.assert_allclose(s_gpu[mask], ora.reset(mask)[mask], rtol=RTOL)
+
+
+def _shared_slice_run(golden, dev, inv, d, n, G, shuffle_days=5, days=12):
+    """The 200-lane, 40-step recipe of tests/test_oracle_slices_cpu.py on the
+    stand-alone kernels (env_reset_kernel / env_step_kernel<MARKET>) with
+    VecEnv(slice_groups=G), masked resets after every step; the device's own done
+    flags drive its resets and the episode bookkeeping the desynchronisation
+    condition is read from."""
+    from tests.test_oracle_slices_cpu import N, SEED, T, groups_desynced, slice_actions, slice_market_kw
+
+    kw = slice_market_kw(golden, d, n, shuffle_days=shuffle_days, days=days)
+    env = _venv(oe.MARKET, inv, N, n, seed=SEED, slice_groups=G, **kw)
+    ora = oe.OracleVecEnv(oe.MARKET, inv, N, n, seed=SEED, slice_groups=G, **kw)
+    np.testing.assert_array_equal(env.lane_start(), ora.start)  # the constructor's reset
+    np.testing.assert_allclose(env.reset().cpu().numpy(), ora.reset(), rtol=RTOL)
+    np.testing.assert_array_equal(env.lane_start(), ora.start)
+    rng = np.random.default_rng(5)
+    ep_dev = np.ones(N, dtype=np.int64)  # the constructor's reset is episode 0
+    desync, resets = [], 0
+    for t in range(T):
+        a = slice_actions(rng, N, env.action_dim)
+        ns, r, dn, risk = (x.cpu().numpy() for x in env.step(torch.from_numpy(a).to(dev)))
+        ons, orr, od, orisk = ora.step(a)
+        np.testing.assert_array_equal(dn.astype(bool), od, err_msg=f"t={t}")
+        np.testing.assert_allclose(ns, ons, rtol=RTOL, err_msg=f"t={t} state")
+        np.testing.assert_allclose(r, orr, rtol=RTOL, err_msg=f"t={t} reward")
+        np.testing.assert_allclose(risk, orisk, rtol=RTOL, equal_nan=True, err_msg=f"t={t} risk")
+        mask = dn[:, 0].astype(bool)
+        if mask.any():
+            s_gpu = env.reset(torch.from_numpy(mask).to(dev)).cpu().numpy()
+            np.testing.assert_allclose(s_gpu[mask], ora.reset(mask)[mask], rtol=RTOL, err_msg=f"t={t} reset")
+            np.testing.assert_array_equal(env.lane_start(), ora.start, err_msg=f"t={t} start")
+            ep_dev[mask] += 1
+            resets += int(mask.sum())
+        desync.append(groups_desynced(ep_dev, G))
+    np.testing.assert_array_equal(ep_dev, ora.episode)
+    w, tt = env.lane_state()
+    np.testing.assert_allclose(w, ora.wealth, rtol=RTOL)
+    np.testing.assert_array_equal(tt, ora.time)
+    assert resets > N  # early ends (lev_max) and the 12-day limit
+    return desync, env, ora
+
+
+@pytest.mark.parametrize("G", [1, 3, 64, 200, 207])
+@pytest.mark.parametrize("inv,d,n", [(oe.INV_A, 1, 1), (oe.INV_C, 3, 2)])
+def test_market_shared_slice_lanes_match_oracle(golden, dev, inv, d, n, G):
+    """slice_groups = G on the stand-alone reset and step kernels: slice_key() in
+    env_reset_lane's start draw and market_row's block permutations.  G = 1 is C4's
+    regime, 3 and 64 leave groups of several lanes (3 does not divide 64), 200 and
+    207 are G = N and G > N (every lane its own key).  Lanes that end early move
+    on to their key's next slice while their group mates stay (asserted)."""
+    desync, env, ora = _shared_slice_run(golden, dev, inv, d, n, G)
+    if G < 200:
+        assert any(desync), "no group ever held lanes at different episode indices"
+        starts = env.lane_start()
+        for k in range(G):  # equal key and episode index: one start row
+            for e in np.unique(ora.episode[k::G]):
+                assert np.unique(starts[k::G][ora.episode[k::G] == e]).size == 1
+    else:
+        assert not any(desync)  # groups of one lane
+
+
+@pytest.mark.parametrize("inv,d,n,shuffle_days,days", [(oe.INV_A, 1, 1, 16, 40), (oe.INV_C, 3, 2, 2, 12)])
+def test_market_shared_slice_block_size_limits(golden, dev, inv, d, n, shuffle_days, days):
+    """market_perm at its block sizes' limits, slice_groups = 1, stand-alone kernels:
+    16 rows (the largest env.hip accepts: fifteen draws from four Philox calls, all
+    sixteen 4-bit entries of the packed permutation; 41 rows = blocks 16, 16, 9) and
+    2 rows with an odd extract (15 rows: a last block of one row, no draw)."""
+    desync, env, ora = _shared_slice_run(golden, dev, inv, d, n, 1, shuffle_days=shuffle_days, days=days)
+    assert ora.ext_len % 2 == 1 and ora.shuffle_days == shuffle_days
+    assert any(desync)
+
+
+def test_market_negative_slice_groups_mean_per_lane(golden, dev):
+    """rlmd_env_create clamps slice_groups < 0 to 0: per-lane starts after a full reset."""
+    from tests.test_oracle_slices_cpu import N, SEED, slice_market_kw
+
+    kw = slice_market_kw(golden, 1, 1)
+    starts = []
+    for G in (0, -5):
+        env = _venv(oe.MARKET, oe.INV_A, N, 1, seed=SEED, slice_groups=G, **kw)
+        env.reset()
+        starts.append(env.lane_start())
+    np.testing.assert_array_equal(starts[0], starts[1])
+    ora = oe.OracleVecEnv(oe.MARKET, oe.INV_A, N, 1, seed=SEED, slice_groups=-5, **kw)
+    ora.reset()
+    np.testing.assert_array_equal(starts[1], ora.start)
+    assert np.unique(starts[1]).size > N // 4

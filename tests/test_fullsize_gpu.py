@@ -157,26 +157,52 @@ def test_c3_full_size_dice_sh_td3(dev, loss):
     assert np.all(np.isfinite(st[[0, 1, 2, 3, 4, 5, 10]])), st
 
 
-def test_c4_full_size_market_on_stooq_snp(golden, dev):
+@pytest.mark.parametrize("slice_groups", [1, 0])
+def test_c4_full_size_market_on_stooq_snp(golden, dev, slice_groups):
     """C4's per-GPU shard at its size: 8,192 Market_InvA_D1 lanes on the
     S&P 500 closes (stooq_snp, committed data fixture), train slices of 1,000
     days shuffled in blocks of 5, SAC 256/256 bf16, K = 8 updates of B = 512;
     every step's ring rows replayed through the oracle env
     (envs/market_envs.py:133-202, env_resources.py:203-291 with the Philox
     starts / permutations), then one evaluation event (100 episodes x 250
-    test days, blocks of 3, gaps 5..20) on the device."""
+    test days, blocks of 3, gaps 5..20) on the device.
+    The keywords are those of bench.market_kwargs().  slice_groups = 1 is what
+    bench.py times and the convergence run trains on: every lane on the one shared
+    slice stream (the fused act_env_kernel<MARKET, 1, 256, ...> with slice_key() = 0
+    for every lane; asserted fused), so all 8,192 lanes report one lane_start()
+    while at one episode index (asserted before the run on all lanes, after it per
+    episode index); 0 is the per-lane regime this test ran before it was
+    parametrised.  The oracle builds one row map per (key, episode, start), so the
+    shared case costs seconds where the per-lane one builds 8,192 maps."""
     from rlmd_amd import _abi
     from rlmd_amd.trainer import VecTrainer
 
     N, T, K, cap, seed = 8192, 12, 8, 1 << 20, 0
     prices = golden("stooq_snp.npz")["prices"]
-    kw = dict(prices=prices, obs_days=1, time_length=1000, shuffle_days=5, sample_days=1000 + 250 + 1 + 20 - 1)
+    kw = dict(prices=prices, obs_days=1, time_length=1000, shuffle_days=5, sample_days=1000 + 250 + 1 + 20 - 1,
+              slice_groups=slice_groups)
     tr = VecTrainer("market", "A", N, algo="SAC", k_updates=K, replay_capacity=cap, seed=seed, warmup_steps=0,
                     smoothing_window=0, precision="bf16", device=dev, init_seed=seed, **kw)
     ora = oe.OracleVecEnv(oe.MARKET, oe.INV_A, N, 1, seed=seed, **kw)
+    start0 = np.unique(tr.env.lane_start())
+    # without the oracle: at 1 all 8,192 lanes report one lane_start() value
+    assert start0.size == 1 if slice_groups == 1 else start0.size > N // 4
+    tr.episode_log(256)
     _replay_steps(tr, ora, T, cap, atol=1e-45)
     assert tr.last_fused()
     np.testing.assert_array_equal(tr.env.lane_start(), ora.start)
+    if slice_groups == 1:
+        # ... and still do after the run, while they are at the same episode index: a
+        # policy action can end a lane's episode early (lev_min: |3 a| < MIN_WEIGHT; among
+        # these 98,304 actions it happens), and that lane moves on to the shared stream's
+        # next slice.  By the device's own episode rows: every lane still in its first
+        # episode is on the first slice, lanes that finished equally many episodes share one.
+        rows, dropped = tr.drain_episodes()
+        done_eps = np.bincount(rows[:, 1].astype(np.int64), minlength=N)
+        starts = tr.env.lane_start()
+        assert dropped == 0 and (done_eps == 0).sum() > N - N // 100
+        assert np.all(starts[done_eps == 0] == start0[0])
+        assert all(np.unique(starts[done_eps == e]).size == 1 for e in np.unique(done_eps))
     sc = tr.agent.scalars()
     assert sc["learn_step_cntr"] == T * K and sc["nan_flag"] == 0
     ev = tr.evaluate_market(n_eval=100, test_days=250)

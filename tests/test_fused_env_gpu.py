@@ -30,7 +30,8 @@ import pytest
 import torch
 
 from oracle import envs as oe
-from tests.test_train_gpu import _market_kw, read_ring
+from tests.test_oracle_slices_cpu import groups_desynced
+from tests.test_train_gpu import _market_kw, desync_trainer, read_ring
 
 pytestmark = pytest.mark.gpu
 
@@ -46,13 +47,17 @@ def _lib():
     return _abi.lib()
 
 
-def _trainer(dev, golden, env, inv, algo, N, T, k=0, seed=11, n=1, obs_days=1):
+def _trainer(dev, golden, env, inv, algo, N, T, k=0, seed=11, n=1, obs_days=1, slice_groups=None):
+    """The trainer and the env keywords it was built with; slice_groups (market)
+    goes to VecTrainer and, through the returned keywords, to OracleVecEnv."""
     from rlmd_amd.trainer import VecTrainer
 
     kw = {}
     if env == "market":  # n assets: stooq_usei's first n columns
         kw = _market_kw(golden, obs_days)
         kw["prices"] = np.ascontiguousarray(kw["prices"][:, :n])
+        if slice_groups is not None:
+            kw["slice_groups"] = slice_groups
     return VecTrainer(env=env, investor=inv, n_lanes=N, n_gambles=n, algo=algo, k_updates=k, seed=seed,
                       init_seed=seed, warmup_steps=0, smoothing_window=0, replay_capacity=N * T, precision="bf16",
                       device=dev, **kw), kw
@@ -77,18 +82,51 @@ def test_wide_shapes_match_oracle(golden, dev, env, inv, n, obs_days, algo):
     _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days)
 
 
-def _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days):
-    N, T, seed = 4000, 16, 11  # 4000 lanes: a ragged last 64-lane block
-    tr, kw = _trainer(dev, golden, env, inv, algo, N, T, seed=seed, n=n, obs_days=obs_days)
-    tr.set_fused(1)
+# slice_groups = G: market A / B / C at one asset and one day (C: the wide-action
+# instantiation), and the run-time-n instantiations at 2 assets x 3 days and 5 days
+SLICED = [("market", "A", 1, 1), ("market", "B", 1, 1), ("market", "C", 1, 1), ("market", "A", 2, 3),
+          ("market", "B", 1, 5)]
+
+
+@pytest.mark.parametrize("algo", ["SAC", "TD3"])
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("env,inv,n,obs_days", SLICED)
+def test_shared_slice_policy_steps_match_oracle(golden, dev, env, inv, n, obs_days, G, fused, algo):
+    """Policy steps at slice_groups = G (1: C4's data regime; 3: groups that do not
+    divide the 64-lane block) against the oracle, 1,000 lanes (15 full 64-lane
+    blocks and a ragged one).  fused = 1 pins act_env_kernel<MARKET, ...>: the
+    epilogue's env_step_lane, wave 1's price prefetch (p0_s / mrel_fill, which
+    calls market_row with its own copy of the lane's start and episode) and the
+    epilogue reset that takes the episode counter from a register (ep_now);
+    fused = 0 pins the acting kernel + env_train_kernel<MARKET, ...>.  Every shape
+    here fuses; which path ran is asserted (rlmd_train_last_fused).  The lanes are
+    out of lock-step from before the first step (test_train_gpu.desync_trainer),
+    so a group's lanes trade different slices at the same time (asserted at every
+    step on the device's own episode rows), and lane_start() equals the oracle's
+    start rows after every step."""
+    _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days, slice_groups=G, fused=fused, N=1000)
+
+
+def _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days, slice_groups=None, fused=1, N=4000):
+    T, seed = 16, 11  # 4000 lanes: a ragged last 64-lane block
+    tr, kw = _trainer(dev, golden, env, inv, algo, N, T, seed=seed, n=n, obs_days=obs_days, slice_groups=slice_groups)
+    tr.set_fused(fused)
     ora = oe.OracleVecEnv(FAMS[env], INVS[inv], N, n, seed=seed, **kw)
     obs = ora.reset()
+    ep_dev = np.zeros(N, dtype=np.int64)  # episode indices by the device's own episode rows
+    if slice_groups is not None:
+        obs = desync_trainer(tr, ora, obs)
+        ep_dev = ora.episode.copy()
+        assert groups_desynced(ep_dev, slice_groups)
     tr.episode_log(64)
     at = 1e-45 if env == "market" else 1e-30
     length = np.ones(N, dtype=np.int64)
     ng1 = n == 1 and obs_days == 1
-    expect_fused = (ora.A <= 2 and (ora.S <= 8 or (env == "market" and ora.S <= 16))) or (
-        ora.A <= 4 and ng1 and ora.S <= 8)
+    expect_fused = bool(fused) and ((ora.A <= 2 and (ora.S <= 8 or (env == "market" and ora.S <= 16))) or (
+        ora.A <= 4 and ng1 and ora.S <= 8))
+    if slice_groups is not None:
+        assert expect_fused == bool(fused)  # every shared-slice shape fuses when allowed to
     ended = 0
     for t in range(T):
         tr.step()
@@ -118,10 +156,17 @@ def _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days):
         obs = ns.copy()
         if m.any():
             obs[m] = ora.reset(m)[m]
+        if slice_groups is not None:
+            np.testing.assert_array_equal(tr.env.lane_start(), ora.start, err_msg=f"t={t} start")
+            ep_dev[rows[:, 1].astype(np.int64)] += 1
+            assert groups_desynced(ep_dev, slice_groups), f"t={t}: the groups' lanes fell back into lock-step"
     np.testing.assert_allclose(tr.obs.cpu().numpy(), obs.astype(np.float32), rtol=1e-6, atol=at)
     assert np.unique(a_r[:, 0]).size > N // 4  # stochastic policy actions
     if env == "market":
         assert ended > 0  # 12-day episodes: lanes finish and restart inside the test
+    if slice_groups is not None:
+        np.testing.assert_array_equal(ep_dev, ora.episode)
+        assert ended >= N  # every lane restarted on its key's next slice
 
 
 @pytest.mark.parametrize("algo", ["SAC", "TD3"])
@@ -133,18 +178,41 @@ def _replay_policy_steps(golden, dev, env, inv, algo, n, obs_days):
 def test_fused_equals_unfused(golden, dev, env, inv, n, obs_days, algo):
     """The statistics' f64 reward sums agree to the bit because both kernels write one
     partial row per 64 lanes (env.hip wave_stats_sum) and one fold adds the rows."""
+    _fused_equals_unfused(golden, dev, env, inv, n, obs_days, algo)
+
+
+@pytest.mark.parametrize("algo", ["SAC", "TD3"])
+@pytest.mark.parametrize("env,inv,n,obs_days", [("market", "A", 1, 1), ("market", "B", 1, 5)])
+def test_fused_equals_unfused_shared_slice(golden, dev, env, inv, n, obs_days, algo):
+    """test_fused_equals_unfused at slice_groups = 1 (C4's data regime), learning on:
+    act_env_kernel<MARKET, 1 | 0, ...> (price prefetch on wave 1, register episode
+    counter in the epilogue reset) against the acting kernel + env_train_kernel
+    <MARKET, 1 | 0, ...>, which reads the relative prices and the episode counter
+    from memory in the step itself: bit-identical rings, wealth, parameters and
+    episode logs, and one lane_start() value over all lanes."""
+    _fused_equals_unfused(golden, dev, env, inv, n, obs_days, algo, slice_groups=1)
+
+
+def _fused_equals_unfused(golden, dev, env, inv, n, obs_days, algo, slice_groups=None):
     N, T = 2048, 12
     out = []
     for fused in (1, 0):
-        tr, _ = _trainer(dev, golden, env, inv, algo, N, T, k=1, seed=5, n=n, obs_days=obs_days)
+        tr, _ = _trainer(dev, golden, env, inv, algo, N, T, k=1, seed=5, n=n, obs_days=obs_days,
+                         slice_groups=slice_groups)
         tr.set_fused(fused)  # per env handle
-        tr.episode_log(64)
+        tr.episode_log(64 if slice_groups is None else 256)  # 256: no row dropped, the starts are grouped by them
         for t in range(T):
             tr.step()
             assert tr.last_fused() == bool(fused)
         ring = read_ring(tr, 0, N * T)
         w, tt = tr.env.lane_state()
-        out.append((ring, w, tt, tr.obs.cpu().numpy(), tr.agent.params.cpu().numpy().copy(), tr.drain_episodes(),
+        eps = tr.drain_episodes()
+        if slice_groups == 1:  # one key: lanes that finished equally many episodes share the slice
+            done_eps = np.bincount(eps[0][:, 1].astype(np.int64), minlength=N)
+            assert eps[1] == 0 and done_eps.min() >= 1  # the 12 steps end every lane's episode 0
+            starts = tr.env.lane_start()
+            assert all(np.unique(starts[done_eps == e]).size == 1 for e in np.unique(done_eps))
+        out.append((ring, w, tt, tr.obs.cpu().numpy(), tr.agent.params.cpu().numpy().copy(), eps,
                     tr.episode_stats()))
         del tr
     (ra, wa, ta, oa, pa, (ea, da), sa), (rb, wb, tb, ob, pb, (eb, db), sb) = out

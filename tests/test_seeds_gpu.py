@@ -33,18 +33,25 @@ def _kw(golden, config):
     if config == "c2":
         return dict(env="gbm", investor="A", n_lanes=8192, algo="SAC")
     prices = golden("stooq_snp.npz")["prices"]
-    return dict(env="market", investor="A", n_lanes=4096, algo="SAC", prices=prices, obs_days=1, time_length=1000,
-                shuffle_days=5, sample_days=1000 + 250 + 1 + 20 - 1)
+    kw = dict(env="market", investor="A", n_lanes=4096, algo="SAC", prices=prices, obs_days=1, time_length=1000,
+              shuffle_days=5, sample_days=1000 + 250 + 1 + 20 - 1)
+    if config == "c4s":  # C4 as it is benched: one shared slice stream
+        kw["slice_groups"] = 1
+    return kw
 
 
 @pytest.mark.parametrize("config,T,streams", [("c2", 2, "pool"), ("c2", 4, "pool"), ("c4", 2, "pool"), ("c4", 4, "pool"),
                                               ("c2", 3, "hip"), ("c2", 3, "cu"), ("c2", 3, "cu_split"),
-                                              ("c4", 4, "cu_split")])
+                                              ("c4", 4, "cu_split"), ("c4s", 2, "pool"), ("c4s", 4, "cu_split")])
 def test_seed_group_bit_equal_to_solo(golden, dev, config, T, streams):
     """streams="hip": the group's streams come from the library's runtime
     (rlmd_stream_create) instead of torch's pool; "cu" / "cu_split": CU-masked
     streams (rlmd_stream_create_cu, every CU / a 1/T interleaved share each).
-    A CU mask only restricts where workgroups run, so results stay bit-equal."""
+    A CU mask only restricts where workgroups run, so results stay bit-equal.
+    "c4s": the C4 shape at slice_groups = 1, the benched data regime (two warm-up
+    steps through env_train_kernel<MARKET, 1, ...>, then act_env_kernel<MARKET, 1,
+    256, ...>, asserted fused): each seed's lanes share that seed's slice stream,
+    and the streams of different seeds differ."""
     from rlmd_amd.trainer import SeedGroup, VecTrainer
 
     steps, K = 6, 4
@@ -57,6 +64,12 @@ def test_seed_group_bit_equal_to_solo(golden, dev, config, T, streams):
     grp.synchronize()
     got = [_state(tr, steps, kw["n_lanes"]) for tr in grp.trainers]
     assert all(tr.last_fused() for tr in grp.trainers)  # the post-window steps fused, per handle
+    if config == "c4s":
+        # lanes still in their first episode (time = steps + 1; a warm-up action may end one early)
+        first = [tr.env.lane_state()[1] == steps + 1 for tr in grp.trainers]
+        starts = [np.unique(tr.env.lane_start()[f]) for tr, f in zip(grp.trainers, first)]
+        assert all(f.sum() > kw["n_lanes"] // 2 for f in first)
+        assert all(s.size == 1 for s in starts) and np.unique(np.concatenate(starts)).size > 1
     for i, s in enumerate(seeds):
         solo = VecTrainer(seed=s, init_seed=s, device=dev, cu_budget=grp.cu_budget, **kw)
         for _ in range(steps):

@@ -45,6 +45,28 @@ def _market_kw(golden, obs_days):
                 shuffle_days=5, sample_days=12 + obs_days + 40)
 
 
+def desync_trainer(tr, ora, obs):
+    """Take a fresh trainer's market lanes out of lock-step without touching
+    product code: policy and warm-up actions end 12-day episodes only on time, so
+    every lane of a fresh trainer sits at episode 0.  Before the first step the
+    lanes with lane % 3 == 1, then those with lane % 5 == 2, are reset through the
+    env handle (env_reset_kernel: the next episode's slice), the returned f64
+    reset states are written into the trainer's f32 observation buffer (the
+    kernels read it through the pointer every step), and the oracle does the same
+    resets.  Lanes then sit at episode 0, 1 or 2 inside every slice group of more
+    than a few lanes, and since all still end on time together, they stay apart."""
+    N = ora.N
+    for mod, rem in ((3, 1), (5, 2)):
+        mask = (np.arange(N) % mod) == rem
+        m_dev = torch.from_numpy(mask).to(tr.device)
+        st = tr.env.reset(m_dev)
+        tr.obs[m_dev] = st[m_dev].to(torch.float32)
+        obs[mask] = ora.reset(mask)[mask]
+    np.testing.assert_array_equal(tr.env.lane_start(), ora.start)
+    np.testing.assert_array_equal(tr.obs.cpu().numpy(), obs.astype(np.float32))
+    return obs
+
+
 @pytest.mark.parametrize("env,inv,fam,oinv,n", [("gbm", "A", oe.GBM, oe.INV_A, 1), ("coin", "B", oe.COIN, oe.INV_B, 2),
                                                 ("dice_sh", "C", oe.DICE_SH, oe.INV_C, 1),
                                                 ("market", "B", oe.MARKET, oe.INV_B, 3),
@@ -54,6 +76,21 @@ def test_warmup_steps_fill_ring_like_oracle(golden, dev, env, inv, fam, oinv, n)
     action samples (|.| unless GBM / market) through the fused step into the
     ring, auto-reset of finished lanes (market: new Philox slice + shuffle;
     n < 0 marks a Dx market env with obs_days 3), episode statistics."""
+    _warmup_steps(golden, dev, env, inv, fam, oinv, n)
+
+
+@pytest.mark.parametrize("inv,oinv,n", [("A", oe.INV_A, 1), ("B", oe.INV_B, 3)])
+def test_warmup_steps_fill_ring_like_oracle_shared_slice(golden, dev, inv, oinv, n):
+    """The same at slice_groups = 1 (C4's data regime): env_train_kernel's
+    random-action path (two launches, no acting kernel), its auto-resets drawing
+    the next shared slice from slice_key() = 0 at the lane's own episode index.
+    Lanes are taken out of lock-step first (desync_trainer), so the one group
+    holds lanes at three episode indices throughout (asserted); lane_start()
+    equals the oracle's after every step."""
+    _warmup_steps(golden, dev, "market", inv, oe.MARKET, oinv, n, slice_groups=1)
+
+
+def _warmup_steps(golden, dev, env, inv, fam, oinv, n, slice_groups=None):
     from rlmd_amd.trainer import VecTrainer
 
     N, T, seed = 512, 25, 17
@@ -61,11 +98,19 @@ def test_warmup_steps_fill_ring_like_oracle(golden, dev, env, inv, fam, oinv, n)
     if fam == oe.MARKET:
         kw = _market_kw(golden, 1 if n > 0 else 3)
         n = abs(n)
+        kw["prices"] = np.ascontiguousarray(kw["prices"][:, :n])
+    if slice_groups is not None:
+        kw["slice_groups"] = slice_groups
     tr = VecTrainer(env=env, investor=inv, n_lanes=N, n_gambles=n, algo="SAC", k_updates=0, seed=seed,
                     warmup_steps=10_000, smoothing_window=20_000, replay_capacity=N * T, precision="fp32",
                     device=dev, **kw)
     ora = oe.OracleVecEnv(fam, oinv, N, n, seed=seed, **kw)
     obs = ora.reset()
+    ep_dev = np.zeros(N, dtype=np.int64)  # episode indices by the device's own episode rows
+    if slice_groups is not None:
+        obs = desync_trainer(tr, ora, obs)
+        ep_dev = ora.episode.copy()
+        assert np.unique(ep_dev).size == 3
     tr.episode_log(64)  # per-episode rows, drained every step (at most 64 per wave per step)
     absw = fam not in (oe.GBM, oe.MARKET)
     at = 1e-45 if fam == oe.MARKET else 1e-30  # market states are O(1e-30) (MAX_VALUE 1e34)
@@ -98,6 +143,11 @@ def test_warmup_steps_fill_ring_like_oracle(golden, dev, env, inv, fam, oinv, n)
         length[m] = 1
         if m.any():
             obs[m] = ora.reset(m)[m]
+        if slice_groups is not None:
+            assert not tr.last_fused()  # warm-up: the two-launch env_train_kernel
+            np.testing.assert_array_equal(tr.env.lane_start(), ora.start, err_msg=f"t={t} start")
+            ep_dev[rows[:, 1].astype(np.int64)] += 1
+            assert np.unique(ep_dev).size >= 3, f"t={t}: the group's lanes fell back into lock-step"
         if t in (7, 8, T - 1):  # flushed reads, also back to back (nothing pending the second time)
             n_ep, r_sum, l_sum, _ = tr.flush_stats().cpu().numpy()
             assert n_ep == exp_n, f"t={t}"
@@ -105,6 +155,9 @@ def test_warmup_steps_fill_ring_like_oracle(golden, dev, env, inv, fam, oinv, n)
     np.testing.assert_allclose(tr.obs.cpu().numpy(), obs.astype(np.float32), rtol=1e-6, atol=at)
     st = tr.episode_stats()
     assert st["episodes"] == exp_n
+    if slice_groups is not None:
+        np.testing.assert_array_equal(ep_dev, ora.episode)
+        assert exp_n >= N  # every lane's 12-day episode ended and restarted
 
 
 def _flat_init(algo, S, A, h1, h2, init):
