@@ -80,6 +80,66 @@ def uniform_draws(seed, lanes, step, tag, count):
     return out
 
 
+MASK64 = (1 << 64) - 1
+EPS32 = float(np.finfo(np.float32).eps)
+BELOW_ONE32 = np.float32(1.0) - np.float32(2.0 ** -24)  # 0x1.fffffep-1, the largest f32 below 1
+
+
+def act_key(seed):
+    """Philox key of the acting noise (rlmd_agent_act, the fused train step) for an
+    agent built with `seed`; counter = noise_ctr / the trainer's cum_step, rows =
+    observation rows / lanes, tag TAG_ACT_NOISE."""
+    return (int(seed) ^ 0xac7ac7ac7) & MASK64
+
+
+def learn_key(seed):
+    """Philox key of the update's policy noise: the agent seed itself; rows = the
+    mini-batch rows, tags TAG_EPS_NEXT / TAG_EPS_CUR (SAC) and TAG_TD3_TARGET."""
+    return int(seed) & MASK64
+
+
+def learn_noise_ctr(updates_done):
+    """Counter of the update's policy noise: learn_step_cntr AFTER the update's own
+    increment (learn_body's ++host_cntr), i.e. the number of updates done so far
+    (rlmd_agent_scalars' learn_step_cntr) plus one."""
+    return int(updates_done) + 1
+
+
+def replay_key(seed):
+    """Philox key of rlmd_agent_learn's replay index draws; update i of a call draws
+    with counter learn_step_cntr (before the call) + i, tag TAG_REPLAY_IDX."""
+    return (int(seed) ^ 0x5eed5eed5eed) & MASK64
+
+
+def policy_noise(dist, seed, rows, ctr, tag, A):
+    """The device's policy noise (rlmd_amd/csrc/rlmd_policy.h policy_draw) restated
+    in float64 and rounded to f32 once: [len(rows), A] float32.
+
+    Component j reads Philox block (seed; row, ctr & 0xFFFFFFFF, tag, j >> 1).
+    "N" / "MVN": Box-Muller on two 24-bit uniforms u1 = (x >> 8) 2^-24, u2 =
+    (z >> 8) 2^-24, r = sqrt(-2 ln(1 - u1)); even j r cos(2 pi u2), odd j
+    r sin(2 pi u2) (the device evaluates this in f32 with the hardware log / sin /
+    cos).  "L": torch's Laplace.rsample uniform w = (eps32 - 1) + (2 - eps32) u in
+    f64 on the 53-bit u01(x, y) (even j) / u01(z, w) (odd j), cast to f32 and
+    capped at the largest f32 below 1."""
+    rows = np.asarray(rows, dtype=np.uint64).reshape(-1)
+    out = np.empty((rows.size, A), dtype=np.float32)
+    for blk in range((A + 1) // 2):
+        v = philox(seed, rows, int(ctr) & 0xFFFFFFFF, tag, blk)
+        if dist == "L":
+            pair = [np.minimum(((EPS32 - 1.0) + (2.0 - EPS32) * u).astype(np.float32), BELOW_ONE32)
+                    for u in (u01(v[0], v[1]), u01(v[2], v[3]))]
+        else:
+            u1 = (v[0] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+            u2 = (v[2] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+            r = np.sqrt(-2.0 * np.log(1.0 - u1))
+            pair = [r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)]
+        for k in range(2):
+            if 2 * blk + k < A:
+                out[:, 2 * blk + k] = pair[k]
+    return out
+
+
 def normal_draws(seed, lanes, step, tag, count):
     lanes = np.asarray(lanes)
     out = np.empty((lanes.size, count))

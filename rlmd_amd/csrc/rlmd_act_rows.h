@@ -165,7 +165,7 @@ __device__ __forceinline__ void act_rows(const FusedActArgs& a, unsigned char* s
       hw[nb][h] = rlmd_ldf(rp, base + c, live && h < nh);
     }
   }
-  // the sampling threads' head biases and policy noise (Philox -> f64 Box-Muller):
+  // the sampling threads' head biases and policy noise (Philox -> f32 Box-Muller):
   // independent of the forward pass, so drawn here, under the load latency, not
   // in the epilogue's tail
   float mu_b[kMaxA], ls_b[kMaxA], ein[kMaxA], nz[kMaxA];

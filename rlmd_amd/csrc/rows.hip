@@ -678,10 +678,11 @@ __device__ __forceinline__ HeadBias head_bias(const float* p, const NetOff& ao, 
   return hb;
 }
 
-// The policy noise of a row's first two components (Philox -> f64 Box-Muller /
-// Laplace uniform), drawn at kernel start: it depends on nothing computed, and
-// its f64 log / sincospi chain then overlaps the fragment loads instead of
-// sitting between the two MLPs of the target path.
+// The policy noise of a row's first two components (policy_draw: Philox -> f32
+// Box-Muller on 24-bit uniforms / Laplace uniform), drawn at kernel start: it
+// depends on nothing computed, and its Philox rounds and log / sin / cos chain
+// then overlap the fragment loads instead of sitting between the two MLPs of
+// the target path.
 struct Noise2 {
   float v[2];
 };

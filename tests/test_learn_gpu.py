@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from oracle import learn as ol
+from oracle import philox as px
 from tests.test_oracle_learn import NETS, TNETS, build, sd
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +69,21 @@ def test_learn_matches_reference_golden(golden, dev, case):
         ref_t = ol.flatten({nm: sd(g, f"{case}/step{s}", tn) for nm, tn in zip(NETS, TNETS)}, lay, n)
         np.testing.assert_allclose(ag.params.cpu().numpy(), ref_p, rtol=0, atol=2e-6, err_msg=f"step {s} params")
         np.testing.assert_allclose(ag.target.cpu().numpy(), ref_t, rtol=0, atol=2e-6, err_msg=f"step {s} targets")
+
+
+def assert_stats_close(st, loss_o, lt_o, lp_o, rtol, msg, logtemp=False):
+    """One update's statistics row (loss[11] | logtemp | loss_params[4]) against the
+    oracle's: rtol as given (2e-4 fp32, 1e-4 bf16), atol 1e-6; logtemp: also SAC's
+    log temperature."""
+    ref = np.concatenate([np.asarray(loss_o, np.float64), np.asarray(lp_o, np.float64)])
+    got = np.concatenate([st[:11], st[12:16]])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.abs(got - ref) / np.maximum(np.abs(ref), 1e-30)
+    print(f"{msg} statistics: max relative difference {np.nanmax(rel):.3g}")
+    np.testing.assert_allclose(st[:11], loss_o, rtol=rtol, atol=1e-6, equal_nan=True, err_msg=msg)
+    np.testing.assert_allclose(st[12:16], lp_o, rtol=rtol, atol=1e-6, err_msg=f"{msg} loss_params")
+    if logtemp:
+        np.testing.assert_allclose(st[11], lt_o, rtol=1e-5, atol=1e-7, err_msg=f"{msg} logtemp")
 
 
 def assert_params_close(got, ref, lr, msg, max_lr_frac=0.1):
@@ -122,12 +138,28 @@ def _random_batch(rng, B, S, A):
     return s, a, r, s2, d
 
 
+def philox_noise(algo, s_dist, seed, updates_done, B, A, swap=False):
+    """(eps_a, eps_b) the device draws for itself in the update after
+    `updates_done` updates of an agent built with `seed` (learn_batch / learn
+    without injected noise), restated by oracle.philox.policy_noise: eps_a is the
+    next-action noise (SAC, tag EPS_NEXT) or the target smoothing noise (TD3, tag
+    TD3_TARGET, always normal), eps_b the current-action noise (EPS_CUR).
+    swap: eps_a drawn under EPS_CUR's tag instead (a control)."""
+    dist = s_dist if algo == "SAC" else "N"
+    key, ctr, rows = px.learn_key(seed), px.learn_noise_ctr(updates_done), np.arange(B)
+    tag_a = px.TAG_EPS_CUR if swap else (px.TAG_EPS_NEXT if algo == "SAC" else px.TAG_TD3_TARGET)
+    return (torch.from_numpy(px.policy_noise(dist, key, rows, ctr, tag_a, A)),
+            torch.from_numpy(px.policy_noise(dist, key, rows, ctr, px.TAG_EPS_CUR, A)))
+
+
 @functools.lru_cache(maxsize=4)
-def _fp32_reference(algo, S, A, h1, h2, B, k, loss, s_dist, dup, steps, okw):
+def _fp32_reference(algo, S, A, h1, h2, B, k, loss, s_dist, dup, steps, okw, philox_seed=None, swap=False):
     """The autograd oracle's run of one case, computed once and shared by the
     tests that send the same case down different device paths: (initial
     parameters, layout, [per update: the mini-batch and noise, the oracle's
-    statistics, its parameters and targets after the update])."""
+    statistics, its parameters and targets after the update]).  philox_seed: the
+    noise is what an agent of that seed draws for itself (philox_noise) in updates
+    0 .. steps - 1 of its life, not the generator's."""
     from rlmd_amd.agent import reference_init
 
     init = reference_init(algo, S, A, h1, h2, seed=11)
@@ -142,8 +174,11 @@ def _fp32_reference(algo, S, A, h1, h2, B, k, loss, s_dist, dup, steps, okw):
     out = []
     for step in range(steps):
         s, a, r, s2, d = _random_batch(rng, B, S, A)
-        ea = torch.from_numpy(draw().astype(np.float32))
-        eb = torch.from_numpy(draw().astype(np.float32))
+        if philox_seed is not None:
+            ea, eb = philox_noise(algo, s_dist, philox_seed, step, B, A, swap)
+        else:
+            ea = torch.from_numpy(draw().astype(np.float32))
+            eb = torch.from_numpy(draw().astype(np.float32))
         if dup:  # rows 2i + 1 repeat rows 2i: equal losses and actor objectives, ranked by row
             for x in (s, a, r, s2, d, ea, eb):
                 x[1::2] = x[0::2]
@@ -156,23 +191,29 @@ def _fp32_reference(algo, S, A, h1, h2, B, k, loss, s_dist, dup, steps, okw):
 @pytest.mark.parametrize("algo,S,A,h1,h2,B,k", FULL)
 @pytest.mark.parametrize("loss", ["MSE", "HUB", "MAE", "HSC"])
 def test_full_size_fp32_matches_oracle(dev, algo, S, A, h1, h2, B, k, loss, max_lr_frac=0.1, s_dist="N", dup=False,
-                                       steps=4, agent_kw=None, cu_budget=None, check_logtemp=False):
+                                       steps=4, agent_kw=None, cu_budget=None, check_logtemp=False,
+                                       philox_seed=None, noise_swap=False):
     """agent_kw: DeviceAgent settings away from their defaults (the oracle takes
     the same under its own names); cu_budget: rlmd_agent_set_cu_budget before
-    the first update; check_logtemp: also compare SAC's log temperature."""
+    the first update; check_logtemp: also compare SAC's log temperature.
+    philox_seed: the agent is built with this seed and draws its own noise
+    (learn_batch without eps, the training loop's branch); the oracle is fed the
+    restated draw (philox_noise; noise_swap: its control)."""
     agent_kw = agent_kw or {}
+    philox = philox_seed is not None
     init, lay, n, ref = _fp32_reference(algo, S, A, h1, h2, B, k, loss, s_dist, dup, steps,
-                                        tuple(sorted(oracle_kw(agent_kw).items())))
-    ag = device_agent(algo, S, A, h1, h2, B, k, loss, init, policy_dist=s_dist, **agent_kw)
+                                        tuple(sorted(oracle_kw(agent_kw).items())), philox_seed, noise_swap)
+    ag = device_agent(algo, S, A, h1, h2, B, k, loss, init, policy_dist=s_dist,
+                      **(dict(agent_kw, seed=philox_seed) if philox else agent_kw))
     if cu_budget is not None:
         set_cu_budget(ag, cu_budget)
     lr = lr_of(algo, lay, n, agent_kw)
     for step, ((s, a, r, s2, d, ea, eb), loss_o, lt_o, lp_o, P_o, T_o) in enumerate(ref):
+        if philox:  # the counter the reference's noise was drawn for
+            assert ag.scalars()["learn_step_cntr"] == step
+            ea = eb = None
         st = ag.learn_batch(s, a, r, s2, d, ea, eb if algo == "SAC" else None).double().cpu().numpy()
-        np.testing.assert_allclose(st[:11], loss_o, rtol=2e-4, atol=1e-6, equal_nan=True, err_msg=f"step {step}")
-        np.testing.assert_allclose(st[12:16], lp_o, rtol=2e-4, atol=1e-6)
-        if check_logtemp and algo == "SAC":
-            np.testing.assert_allclose(st[11], lt_o, rtol=1e-5, atol=1e-7, err_msg=f"step {step} logtemp")
+        assert_stats_close(st, loss_o, lt_o, lp_o, 2e-4, f"step {step}", check_logtemp and algo == "SAC")
         assert_params_close(ag.params.cpu().numpy(), P_o, lr, f"step {step} params", max_lr_frac)
         assert_params_close(ag.target.cpu().numpy(), T_o, lr, f"step {step} targets", max_lr_frac)
 
@@ -224,8 +265,27 @@ def test_batch_1024_separate_actor_loss(dev, algo):
     test_full_size_fp32_matches_oracle(dev, algo, 5, 1, 256, 256, 1024, 512, "MSE", max_lr_frac=0.2)
 
 
+def ill_conditioned(ora):
+    """The elements the bf16 oracle's last update stepped with |g| < 1e-6."""
+    return np.abs(np.nan_to_num(ora.last_grad.numpy(), nan=1.0)) < 1e-6
+
+
+def assert_bf16_state_close(ag, ora, ill, lr, msg, max_lr_frac=0.1):
+    """Device parameters and targets against the bf16 oracle's.  Bulk: >= 99.9 % of
+    all entries within 2e-6; well-conditioned entries (|g| >= 1e-6 in the updates
+    since the two were equal, `ill` marks the others): all within 10 % of one
+    Adam step."""
+    for nm, got, ref in (("params", ag.params, ora.P), ("targets", ag.target, ora.T)):
+        dp = np.abs(got.cpu().numpy() - ref.numpy())
+        frac = np.mean(dp <= 2e-6)
+        print(f"{msg} {nm}: within 2e-6 {frac:.6f}, max {dp.max():.3g}, "
+              f"max well-conditioned {dp[~ill].max():.3g}, ill-conditioned {ill.mean():.5f}")
+        assert frac >= 0.999, f"{msg} {nm}: only {frac:.6f} within 2e-6"
+        assert np.all((dp <= max_lr_frac * lr) | ill), f"{msg} {nm}: {dp[~ill].max():.3g} > {max_lr_frac:.0%} of lr"
+
+
 def bf16_vs_oracle(algo, S, A, h1, h2, B, k, loss, steps=4, seed=5, path="fused", actor_path=None, agent_kw=None,
-                   cu_budget=None, max_lr_frac=0.1):
+                   cu_budget=None, max_lr_frac=0.1, philox_seed=None):
     """The headline precision's learner against the bf16 oracle (oracle/learn.py
     precision="bf16"), state rows O(1) so that the bf16 operands carry signal.
     Every oracle update starts from the device's state (parameters, targets,
@@ -234,7 +294,8 @@ def bf16_vs_oracle(algo, S, A, h1, h2, B, k, loss, steps=4, seed=5, path="fused"
     its own arithmetic, over consecutive updates (Adam step counts, Polyak and
     TD3's delayed actor steps).  actor_path: the oracle's form of the actor half
     when it differs from the critic's (A > 2 on the fused critic step);
-    agent_kw / cu_budget as in test_full_size_fp32_matches_oracle."""
+    agent_kw / cu_budget / philox_seed as in test_full_size_fp32_matches_oracle
+    (the noise counter read from the device's learn_step_cntr before each update)."""
     from rlmd_amd.agent import reference_init
 
     init = reference_init(algo, S, A, h1, h2, seed=seed)
@@ -244,7 +305,9 @@ def bf16_vs_oracle(algo, S, A, h1, h2, B, k, loss, steps=4, seed=5, path="fused"
                     for nm, tn in zip(NETS, TNETS)}, lay, n)
     ora = ol.OracleLearner(algo, S, A, h1, h2, B, k, loss, p, t, precision="bf16", path=path,
                            actor_path=actor_path, **oracle_kw(agent_kw or {}))
-    ag = device_agent(algo, S, A, h1, h2, B, k, loss, init, precision="bf16", **(agent_kw or {}))
+    philox = philox_seed is not None
+    ag = device_agent(algo, S, A, h1, h2, B, k, loss, init, precision="bf16",
+                      **(dict(agent_kw or {}, seed=philox_seed) if philox else (agent_kw or {})))
     if cu_budget is not None:
         set_cu_budget(ag, cu_budget)
     rng = np.random.default_rng(seed + 100)
@@ -262,25 +325,15 @@ def bf16_vs_oracle(algo, S, A, h1, h2, B, k, loss, steps=4, seed=5, path="fused"
         s2 = torch.from_numpy(rng.normal(0, 1, (B, S)).astype(np.float32))
         ea = torch.from_numpy(rng.standard_normal((B, A)).astype(np.float32))
         eb = torch.from_numpy(rng.standard_normal((B, A)).astype(np.float32))
-        st = ag.learn_batch(s, a, r, s2, d, ea, eb if algo == "SAC" else None).double().cpu().numpy()
+        if philox:
+            ea, eb = philox_noise(algo, "N", philox_seed, sc["learn_step_cntr"], B, A)
+            st = ag.learn_batch(s, a, r, s2, d, None, None).double().cpu().numpy()
+        else:
+            st = ag.learn_batch(s, a, r, s2, d, ea, eb if algo == "SAC" else None).double().cpu().numpy()
         lo, lt_o, lp_o = ora.learn(s.numpy(), a.numpy(), r.numpy(), s2.numpy(), d.numpy(), ea.numpy(),
                                    eb.numpy() if algo == "SAC" else None)
-        np.testing.assert_allclose(st[:11], lo, rtol=1e-4, atol=1e-6, equal_nan=True, err_msg=f"step {step}")
-        np.testing.assert_allclose(st[12:16], lp_o, rtol=1e-4, atol=1e-6, err_msg=f"step {step} loss_params")
-        if algo == "SAC":
-            np.testing.assert_allclose(st[11], lt_o, rtol=1e-5, atol=1e-7)
-        g = ora.last_grad.numpy()
-        ill = np.abs(np.nan_to_num(g, nan=1.0)) < 1e-6  # this update's ill-conditioned elements
-        # bulk: >= 99.9 % of all parameters within 2e-6; well-conditioned elements
-        # (|g| >= 1e-6 in this update): all within 10 % of one Adam step
-        for nm, got, ref in (("params", ag.params, ora.P), ("targets", ag.target, ora.T)):
-            dp = np.abs(got.cpu().numpy() - ref.numpy())
-            frac = np.mean(dp <= 2e-6)
-            print(f"{algo} {loss} step {step} {nm}: within 2e-6 {frac:.6f}, max {dp.max():.3g}, "
-                  f"max well-conditioned {dp[~ill].max():.3g}, ill-conditioned {ill.mean():.5f}")
-            assert frac >= 0.999, f"step {step} {nm}: only {frac:.6f} within 2e-6"
-            assert np.all((dp <= max_lr_frac * lr) | ill), \
-                f"step {step} {nm}: {dp[~ill].max():.3g} > {max_lr_frac:.0%} of lr"
+        assert_stats_close(st, lo, lt_o, lp_o, 1e-4, f"step {step}", algo == "SAC")
+        assert_bf16_state_close(ag, ora, ill_conditioned(ora), lr, f"{algo} {loss} step {step}", max_lr_frac)
 
 
 @pytest.mark.parametrize("algo,S,A,h1,h2,B,k", FULL[:2])
