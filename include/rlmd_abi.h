@@ -476,6 +476,15 @@ int rlmd_agent_set_cu_budget(rlmd_agent_t ag, int32_t n_cu);
  * rlmd_agent_learn outside the training step, parameters written by the host). */
 int rlmd_agent_hoist_counts(rlmd_agent_t ag, int64_t* out2);
 
+/* Debug query of the row kernels' exact-shape form (RLMD_ROWS_EXACT, default on,
+ * read at agent creation): at bf16 hidden widths 256 / 256 the learner's forward
+ * and q-evaluation launches run instantiations whose layer-2 MFMA loops have their
+ * band and K-step counts at compile time; every other shape, and every shape
+ * under RLMD_ROWS_EXACT=0, runs the run-time form.  Results are bit-identical.
+ * out2[0] = launches of the two kernels that took the exact form, out2[1] = that
+ * took the run-time form. */
+int rlmd_agent_rows_exact_counts(rlmd_agent_t ag, int64_t* out2);
+
 /* ------------------------------------------------------------- test hooks */
 /* Copy ring rows (start + i) % capacity, i < n, into caller buffers (nullable). */
 int rlmd_replay_read(rlmd_replay_t rb, int64_t start, int64_t n, float* s_dev, float* a_dev,

@@ -121,6 +121,7 @@ SIGNATURES = {
     "rlmd_profile_samples": (C.c_int, [P, I32, P, C.c_int64, P]),
     "rlmd_agent_set_cu_budget": (C.c_int, [P, I32]),
     "rlmd_agent_hoist_counts": (C.c_int, [P, P]),
+    "rlmd_agent_rows_exact_counts": (C.c_int, [P, P]),
     "rlmd_gemm": (C.c_int, [I32, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, I32, P, I32, P, P]),
 }
 

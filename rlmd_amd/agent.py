@@ -237,6 +237,13 @@ class DeviceAgent:
         check(_abi.lib().rlmd_agent_hoist_counts(self.h, out))
         return int(out[0]), int(out[1])
 
+    def rows_exact_counts(self):
+        """(exact, run-time): the learner's fwd_rows / qeval_rows launches by the form
+        they took (rlmd_agent_rows_exact_counts; RLMD_ROWS_EXACT=0: never the exact one)."""
+        out = (C.c_int64 * 2)()
+        check(_abi.lib().rlmd_agent_rows_exact_counts(self.h, out))
+        return int(out[0]), int(out[1])
+
     def scalars(self):
         out = (C.c_double * 5)()
         check(_abi.lib().rlmd_agent_scalars(self.h, out))

@@ -342,6 +342,10 @@ struct rlmd_agent_s {
     uint64_t seed = 0, ctr = 0;
   } pre;
   int64_t n_hoisted = 0, n_fallback = 0;  // calls of agent_learn_k by path (rlmd_agent_hoist_counts)
+  // fwd_rows / qeval_rows may take their exact-shape form (rows.hip rows_exact;
+  // RLMD_ROWS_EXACT=0: never) and the launches of the two by the form they took
+  bool rows_exact_on = true;
+  int64_t n_rows_exact = 0, n_rows_generic = 0;  // rlmd_agent_rows_exact_counts
   size_t wcopy_bytes = 0;  // per copy
   float *act_h1 = nullptr, *act_h2 = nullptr;
   int64_t act_cap = 0;
@@ -760,7 +764,9 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
       f.ctrn = (uint32_t)(cntr + 1);
     }
     if (hc && hc->gathered) f.hg = hc->hg;
-    RLMD_TRY(fwd_rows_launch(f, st, fsplit));
+    bool took = false;
+    RLMD_TRY(fwd_rows_launch(f, st, fsplit, ag->rows_exact_on, &took));
+    (took ? ag->n_rows_exact : ag->n_rows_generic)++;
   }
   // ---- critic loss (algo_sac.py:413-465)
   LossArgs loss_fused{}, loss_stats{};  // B == 0: not used
@@ -906,7 +912,9 @@ int learn_body(rlmd_agent_s* ag, const Batch& mb, const float* eps_a, const floa
         ((B + 15) / 16) * (2 * nq + qe.nab) <= ag->n_cu)
       qsplit = 2;
     qe.split = qsplit;
-    RLMD_TRY(qeval_rows_launch(qe, nq, st, qsplit));
+    bool took = false;
+    RLMD_TRY(qeval_rows_launch(qe, nq, st, qsplit, ag->rows_exact_on, &took));
+    (took ? ag->n_rows_exact : ag->n_rows_generic)++;
     if (ag->fused_actor) {
       // the actor (+ temperature) step in one launch (update.hip)
       ActUpdArgs au{};
@@ -1251,6 +1259,8 @@ int rlmd_agent_create(const rlmd_agent_cfg* cfg, float* params, float* target, f
     ag->target_pair = !(tp && atoi(tp) == 0);
     const char* sh = getenv("RLMD_SAMPLE_HOIST");  // default on; RLMD_SAMPLE_HOIST=0: the sample launch every call
     ag->hoist_on = !(sh && atoi(sh) == 0);
+    const char* re = getenv("RLMD_ROWS_EXACT");  // default on; RLMD_ROWS_EXACT=0: every shape on the run-time form
+    ag->rows_exact_on = !(re && atoi(re) == 0);
     const char* nf = getenv("RLMD_NO_FUSED_UPDATE");
     ag->fused_update = B <= 512 && X <= 8 && !(nf && atoi(nf) != 0);
     const char* na = getenv("RLMD_NO_FUSED_ACTOR");
@@ -1404,6 +1414,13 @@ int rlmd_agent_hoist_counts(rlmd_agent_t ag, int64_t* out2) {
   RLMD_CHECK(ag && out2, "null argument");
   out2[0] = ag->n_hoisted;
   out2[1] = ag->n_fallback;
+  return 0;
+}
+
+int rlmd_agent_rows_exact_counts(rlmd_agent_t ag, int64_t* out2) {
+  RLMD_CHECK(ag && out2, "null argument");
+  out2[0] = ag->n_rows_exact;
+  out2[1] = ag->n_rows_generic;
   return 0;
 }
 

@@ -311,9 +311,14 @@ struct ABwdArgs {
 };
 
 size_t rows_lds_bytes(const RowDims& d);
-int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split = 1);  // split: critic column halves (gridDim.z)
+// split: critic column halves (gridDim.z).  exact: the launch may take the kernels'
+// exact-shape form (rows.hip rows_exact) where the shape is one it is compiled
+// for; took_exact (nullable): whether it did.  Same results either way.
+int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split = 1, bool exact = false,
+                    bool* took_exact = nullptr);
 int fwd_rows_gather_y(int B, int nk);  // grid rows of a.hg's gather role (nk mini-batches) past the jobs
-int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split = 1);  // split: gridDim.z column halves
+int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split = 1, bool exact = false,
+                      bool* took_exact = nullptr);  // split: column halves; exact, took_exact: as fwd_rows_launch
 int cbwd_rows_launch(const CBwdArgs& a, hipStream_t st);
 int abwd_rows_launch(const ABwdArgs& a, hipStream_t st);
 // Compute copies (wc, wt) of fc2.weight for n nets; refresh from the masters.

@@ -39,6 +39,17 @@ constexpr int W1P = 8;        // fc1 inputs of the MFMA layer 1 (two K-steps); w
                               // per thread on the VALU path (more -> read in the loop)
 constexpr int kHeadsMax = 2 * RLMD_MAX_ACTION;
 
+// The wave index.  SCALAR (the exact-shape forms): read through readfirstlane, so
+// what is derived from it — fragment offsets, the partials' slot — is scalar
+// arithmetic.  The run-time forms keep the per-lane value threadIdx.x >> 6: their
+// band guards are exec masks, and as scalar branches they were slower where the
+// K loop streams (TD3 400 / 300: the step 2 % longer).
+template <bool SCALAR>
+__device__ __forceinline__ int wave_id() {
+  if constexpr (SCALAR) return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  else return (int)(threadIdx.x >> 6);
+}
+
 #ifdef RLMD_TIMING
 // experiment builds only (tools/ts_probe.py): thread-0 s_memtime checkpoints of
 // workgroup (0, y) — slots [16 y, 16 y + 16) for fwd jobs, 96.. for abwd
@@ -138,47 +149,81 @@ struct Pre {
 template <int PREC, int NBW, bool MULTI>
 using FragArr = typename CT<PREC>::Frag[Pre<PREC, NBW, MULTI>::G][NBW];
 
-template <int PREC, int NBW, bool MULTI>
+// Exact shapes (LB, NS > 0; the launch picks them from RowDims and the split):
+// every wave owns exactly LB live bands and the call covers exactly NS K-steps
+// from s0, so frag_load / frag_mfma / the epilogues run without a guard and
+// touch no register of a band i >= LB or a group slot g >= NS.  LB = NS = 0: the
+// run-time form for every other shape.
+template <int PREC, int NBW, bool MULTI, int LB = 0, int NS = 0>
 __device__ __forceinline__ void frag_load(FragArr<PREC, NBW, MULTI>& f,
                                           const typename CT<PREC>::T* Bg, int ldb, int s0, int nsteps, int nblk,
                                           int nb0 = 0) {
   constexpr int G = Pre<PREC, NBW, MULTI>::G;
   constexpr int EPF = 16 / sizeof(typename CT<PREC>::T);
   constexpr int TS = sizeof(typename CT<PREC>::T);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  static_assert((LB > 0) == (NS > 0) && LB <= NBW && NS <= G && !(MULTI && NS > 0), "exact shapes: one group, no streaming");
+  const int lane = threadIdx.x & 63, wave = wave_id<(NS > 0)>();
   // fragment-major copy (frag_index): block (band nb, step s) at ((nb * nS + s) * 64 + lane) * EPF;
   // this workgroup's bands are nb0 .. nb0 + nblk - 1 (a column split of the output)
   const int nS = ldb / CT<PREC>::KS;
   const uint32_t base = (uint32_t)(((nb0 + wave) * nS * 64 + lane) * EPF);
   const __amdgpu_buffer_rsrc_t rs = rlmd_rsrc(Bg, (int64_t)(nb0 + nblk) * 16 * ldb * TS);
+  if constexpr (NS > 0) {
 #pragma unroll
-  for (int g = 0; g < G; ++g)
+    for (int g = 0; g < NS; ++g)
 #pragma unroll
-    for (int i = 0; i < NBW; ++i) {
-      const bool ok = wave + NW * i < nblk && s0 + g < nsteps;
-      const uint32_t e = base + (uint32_t)((NW * i * nS + s0 + g) * 64 * EPF);
-      f[g][i] = __builtin_bit_cast(typename CT<PREC>::Frag,
-                                   __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (int)(e * TS) : 0x7fffffff, 0, 0));
-    }
+      for (int i = 0; i < LB; ++i) {
+        const uint32_t e = base + (uint32_t)((NW * i * nS + s0 + g) * 64 * EPF);
+        f[g][i] = __builtin_bit_cast(typename CT<PREC>::Frag, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(e * TS), 0, 0));
+      }
+  } else {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < NBW; ++i) {
+        const bool ok = wave + NW * i < nblk && s0 + g < nsteps;
+        const uint32_t e = base + (uint32_t)((NW * i * nS + s0 + g) * 64 * EPF);
+        f[g][i] = __builtin_bit_cast(typename CT<PREC>::Frag,
+                                     __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? (int)(e * TS) : 0x7fffffff, 0, 0));
+      }
+  }
 }
 
 // K-steps [ks0, K / KS) of output bands nb0 .. nb0 + nblk - 1 (a K split: ks0 > 0
 // with K short of the full depth; a column split: nb0 > 0 with fewer bands)
-template <int PREC, int NBW, bool MULTI>
+template <int PREC, int NBW, bool MULTI, int LB = 0, int NS = 0>
 __device__ __forceinline__ void pre_issue(Pre<PREC, NBW, MULTI>& p, const void* Bg, int ldb, int K, int nblk,
                                           int nb0 = 0, int ks0 = 0) {
-  frag_load<PREC, NBW, MULTI>(p.f, static_cast<const typename CT<PREC>::T*>(Bg), ldb, ks0, K / CT<PREC>::KS, nblk,
+  frag_load<PREC, NBW, MULTI, LB, NS>(p.f, static_cast<const typename CT<PREC>::T*>(Bg), ldb, ks0, K / CT<PREC>::KS, nblk,
                               nb0);
 }
 
-template <int PREC, int NBW, bool MULTI>
+template <int PREC, int NBW, bool MULTI, int LB = 0, int NS = 0>
 __device__ __forceinline__ void frag_mfma(const FragArr<PREC, NBW, MULTI>& f,
                                           const typename CT<PREC>::T* As, int lda, int s0, int nsteps, int nblk,
                                           f32x4 (&acc)[NBW]) {
   constexpr int G = Pre<PREC, NBW, MULTI>::G;
   constexpr int EPF = 16 / sizeof(typename CT<PREC>::T);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = wave_id<(NS > 0)>();
   const int aoff = (lane & 15) * lda + EPF * (lane >> 4);
+  if constexpr (NS > 0) {
+    // every A fragment of the group read in one batch, then each band's chain in
+    // ascending K order from its zero start, the bands' chains interleaved
+    typename CT<PREC>::Frag a[NS];
+#pragma unroll
+    for (int g = 0; g < NS; ++g)
+      a[g] = *reinterpret_cast<const typename CT<PREC>::Frag*>(As + aoff + (s0 + g) * CT<PREC>::KS);
+#pragma unroll
+    for (int g = 0; g < NS; ++g)
+#pragma unroll
+      for (int i = 0; i < LB; ++i) CT<PREC>::mfma(a[g], f[g][i], acc[i]);
+    // keep that order in the schedule: NS LDS reads in flight together (mask
+    // 0x100), then the MFMAs (0x008) — left alone, the scheduler feeds the reads
+    // in two or three ahead of their MFMAs to save registers
+    __builtin_amdgcn_sched_group_barrier(0x100, NS, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, NS * LB * (PREC == RLMD_BF16 ? 1 : 4), 0);
+    return;
+  }
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     if (s0 + g < nsteps) {
@@ -194,7 +239,7 @@ __device__ __forceinline__ void frag_mfma(const FragArr<PREC, NBW, MULTI>& f,
 // acc[i] = A[16 x K] B^T for output column block nb = wave + 8 i (A: LDS rows of
 // pitch lda; B: compute copy, one row of K elements per output column, pitch ldb).
 // ks0: the first K-step (pre issued with the same origin); K / KS the end
-template <int PREC, int NBW, bool MULTI>
+template <int PREC, int NBW, bool MULTI, int LB = 0, int NS = 0>
 __device__ __forceinline__ void mfma_rows(Pre<PREC, NBW, MULTI>& pre, const typename CT<PREC>::T* As, int lda,
                                           const void* Bv, int ldb, int K, int nblk, f32x4 (&acc)[NBW],
                                           int nb0 = 0, int ks0 = 0) {
@@ -205,7 +250,7 @@ __device__ __forceinline__ void mfma_rows(Pre<PREC, NBW, MULTI>& pre, const type
   for (int i = 0; i < NBW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   if constexpr (!MULTI) {
     (void)Bg;
-    frag_mfma<PREC, NBW, MULTI>(pre.f, As, lda, ks0, nsteps, nblk, acc);
+    frag_mfma<PREC, NBW, MULTI, LB, NS>(pre.f, As, lda, ks0, nsteps, nblk, acc);
   } else {
     FragArr<PREC, NBW, MULTI> b1;
     for (int s = ks0; s < nsteps; s += 2 * G) {
@@ -386,18 +431,19 @@ __device__ __forceinline__ void store_rp_rows(typename CT<PREC>::T* base, int64_
 // the dot the VALU form computed per (unit, row) — so the bits are unchanged;
 // the bias is added after it.  A lane ends with 4 rows of one unit per band: the
 // accumulator layout the mask word (m1_index) and the row-packed h1 are stored in.
-template <int PREC, int NBW>
+// FULL (exact shapes): H1p / 16 = NW * NBW, every band of every wave is live.
+template <int PREC, int NBW, bool FULL = false>
 __device__ __forceinline__ void layer1_mfma(const FwdConst<NBW>& k, const NetOff& o, const float* xs, int ldx,
                                             typename CT<PREC>::T* a1, int lda1, float* h1_out, uint8_t* m1_out,
                                             int row0, int B, const FwdExtra<PREC>* ex) {
   using T = typename CT<PREC>::T;
   const int H1 = o.h1, H1p = pad32(H1);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = wave_id<FULL>();
   // xs rows are zero padded to ldx >= W1P: both K-steps read unconditionally
   const float x0 = xs[(lane & 15) * ldx + (lane >> 4)], x1 = xs[(lane & 15) * ldx + 4 + (lane >> 4)];
 #pragma unroll
   for (int i = 0; i < NBW; ++i) {
-    if (wave + NW * i < H1p / 16) {
+    if (FULL || wave + NW * i < H1p / 16) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, k.w1[2 * i], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, k.w1[2 * i + 1], acc, 0, 0, 0);
@@ -434,12 +480,12 @@ __device__ __forceinline__ void layer1_mfma(const FwdConst<NBW>& k, const NetOff
 // States wider than W1P floats: thread = (hidden unit, row group), x rows
 // broadcast from LDS, an fmaf chain over the `in` inputs (a K padded to a
 // multiple of 4 would append fma(0, 0, acc) steps, which turn a -0 sum into +0).
-template <int PREC, int NBW>
+template <int PREC, int NBW, bool FULL = false>
 __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, const NetOff& o, const float* xs,
                                        int ldx, int in, typename CT<PREC>::T* a1, int lda1, float* h1_out,
                                        uint8_t* m1_out, int row0, int B, const FwdExtra<PREC>* ex = nullptr) {
   if (l1_mfma(in)) {
-    layer1_mfma<PREC, NBW>(k, o, xs, ldx, a1, lda1, h1_out, m1_out, row0, B, ex);
+    layer1_mfma<PREC, NBW, FULL>(k, o, xs, ldx, a1, lda1, h1_out, m1_out, row0, B, ex);
     return;
   }
   constexpr int MR = kMR<NBW>;
@@ -509,14 +555,14 @@ __device__ __forceinline__ void layer1(const FwdConst<NBW>& k, const float* p, c
 // the sums (nh <= NH, or nh > NHF: none is written); a slot costs 4 NBW fmaf and a
 // 16-lane sum per row group, so a critic (one head) runs at NH = 1 and one-action
 // SAC / TD3 policies at NH = 2.  Each live head's chain keeps its order.
-template <int NBW, int PREC = RLMD_BF16, int NH = NHF>
+template <int NBW, int PREC = RLMD_BF16, int NH = NHF, int LB = 0>
 __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBW], const FwdConst<NBW>& k, const NetOff& o,
                                              int nh, float* h2_out, uint8_t* m2_out, float* h2s, int ldh2,
                                              float* part, int row0, int B, const FwdExtra<PREC>* ex = nullptr,
                                              int lda1 = 0, int nb0 = 0, int nbw = 0) {
   // output bands nb0 .. nb0 + nbw - 1 (a column split; nbw = 0: all of them)
   const int H2 = o.h2, nblk = nbw ? nbw : pad32(H2) / 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = wave_id<(LB > 0)>();
   using T = typename CT<PREC>::T;
   float ph[4][NH];
 #pragma unroll
@@ -524,8 +570,8 @@ __device__ __forceinline__ void fwd_epilogue(const f32x4 (&acc)[NBW], const FwdC
 #pragma unroll
     for (int h = 0; h < NH; ++h) ph[rg][h] = 0.f;
 #pragma unroll
-  for (int i = 0; i < NBW; ++i) {
-    if (wave + NW * i < nblk) {
+  for (int i = 0; i < (LB ? LB : NBW); ++i) {
+    if (LB || wave + NW * i < nblk) {
       const int col = acc_col(i, nb0);
       const bool cin = col < H2;
       uint32_t mw = 0;
@@ -605,7 +651,8 @@ struct NoHook {
 // job issues its NEXT fragment stream there, under this net's epilogue, instead
 // of with the first load round, where it queued behind (and delayed) this one.
 // NH: the epilogue's head slots at compile time (a critic: 1); 0: chosen from nh.
-template <int PREC, int NBW, bool MULTI, int NH = 0, typename Hook = NoHook>
+// LB, NS: layer 2's exact shape (frag_load); then layer 1's bands are all live too.
+template <int PREC, int NBW, bool MULTI, int NH = 0, int LB = 0, int NS = 0, typename Hook = NoHook>
 __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, const FwdConst<NBW>& k, Pre<PREC, NBW, MULTI>& pre,
                          const float* xs, int ldx, int in, int nh, const float* wa, const float* wb, int na,
                          unsigned char* smem, const Lds& L, float* h1_out, float* h2_out, int row0, int B,
@@ -617,7 +664,7 @@ __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, con
   float* hout = reinterpret_cast<float*>(smem + L.hout);
   float* h2s = reinterpret_cast<float*>(smem + L.h2s);
   (void)ts;  // job 0's stamps (RLMD_TIMING builds): slots ts .. ts + 4
-  layer1<PREC, NBW>(k, net.p, o, xs, ldx, in, a1, L.lda1, h1_out, m1_out, row0, B, ex);
+  layer1<PREC, NBW, (NS > 0)>(k, net.p, o, xs, ldx, in, a1, L.lda1, h1_out, m1_out, row0, B, ex);
   if (blockIdx.y == 2) RLMD_TSR(63);
   if (blockIdx.y == 4) RLMD_TSR(87);
   if (blockIdx.y == 0 && ts >= 0) RLMD_TSR(ts);
@@ -627,7 +674,7 @@ __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, con
   if (blockIdx.y == 0 && ts >= 0) RLMD_TSR(ts + 1);
   f32x4 acc[NBW];
   const int H1p = pad32(o.h1);
-  mfma_rows<PREC, NBW, MULTI>(pre, a1, L.lda1, net.wc, H1p, H1p, nbw ? nbw : pad32(o.h2) / 16, acc, nb0);
+  mfma_rows<PREC, NBW, MULTI, LB, NS>(pre, a1, L.lda1, net.wc, H1p, H1p, nbw ? nbw : pad32(o.h2) / 16, acc, nb0);
   after_l2();
   if (blockIdx.y == 2) RLMD_TSR(65);
   if (blockIdx.y == 4) RLMD_TSR(89);
@@ -635,11 +682,11 @@ __device__ __forceinline__ void mlp_rows(const RowNet& net, const NetOff& o, con
   const bool fused = nh <= NHF;
   float* h2d = fused ? nullptr : h2s;
   if constexpr (NH > 0)
-    fwd_epilogue<NBW, PREC, NH>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
+    fwd_epilogue<NBW, PREC, NH, LB>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
   else if (nh <= 2)
-    fwd_epilogue<NBW, PREC, 2>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
+    fwd_epilogue<NBW, PREC, 2, LB>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
   else
-    fwd_epilogue<NBW, PREC, NHF>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
+    fwd_epilogue<NBW, PREC, NHF, LB>(acc, k, o, nh, h2_out, m2_out, h2d, L.ldh2, part, row0, B, ex, L.lda1, nb0, nbw);
   if (blockIdx.y == 2) RLMD_TSR(66);
   if (blockIdx.y == 4) RLMD_TSR(90);
   if (blockIdx.y == 0 && ts >= 0) RLMD_TSR(ts + 3);
@@ -860,16 +907,16 @@ __device__ __forceinline__ void critic_const(FwdConst<NBW>& k, const RowNet& n, 
 // [R][H2p]) times fc2.weight through the transposed compute copy, masked by
 // [h1 > 0] (m1s) and stored row-packed in f32 (u, [nrb][H1p][16]).
 // K-steps [ks0, ke / KS) of the contraction (a column split: this half's fc2 columns).
-template <int PREC, int NBW, bool MULTI>
+template <int PREC, int NBW, bool MULTI, int LB = 0, int NS = 0>
 __device__ __forceinline__ void basis_pass(Pre<PREC, NBW, MULTI>& pw, const typename CT<PREC>::T* aU, int lda,
                                            const void* wt, int H1p, int H2p, const uint8_t* m1s, float* u, int row0,
                                            int B, int ks0 = 0, int ke = 0) {
   f32x4 acc[NBW];
-  mfma_rows<PREC, NBW, MULTI>(pw, aU, lda, wt, H2p, ke ? ke : H2p, H1p / 16, acc, 0, ks0);
-  const int wave = threadIdx.x >> 6;
+  mfma_rows<PREC, NBW, MULTI, LB, NS>(pw, aU, lda, wt, H2p, ke ? ke : H2p, H1p / 16, acc, 0, ks0);
+  const int wave = wave_id<(LB > 0)>();
 #pragma unroll
-  for (int i = 0; i < NBW; ++i) {
-    if (wave + NW * i < H1p / 16) {
+  for (int i = 0; i < (LB ? LB : NBW); ++i) {
+    if (LB || wave + NW * i < H1p / 16) {
       const int col = acc_col(i);
       f32x4 v;
 #pragma unroll
@@ -887,8 +934,23 @@ __device__ __forceinline__ void basis_pass(Pre<PREC, NBW, MULTI>& pw, const type
 // critic y - 2 on (s, a); y = 4: policy on s for the actor step.
 // GATHER (update 0 of a call with index sets drawn ahead, a.hg): rows staged from
 // the ring by index; grid rows y past the jobs run the gather role.
-template <int PREC, int NBW, bool MULTI, bool GATHER = false>
+// EX (the launch's choice, rows_exact): 0 any shape; 1 H1p = H2p = 16 NW NBW, one
+// group of K-steps, unsplit; 2 the same widths under the column split P = 2.
+// Exact shapes of the MFMA passes (frag_load's LB, NS) under EX:
+//   policy layer 2, head bases      NBW bands, G K-steps
+//   critic layer 2                  NBW bands (EX 2: NBW / 2, this half's), G K-steps
+//   critic basis pass               NBW bands, G K-steps (EX 2: G / 2, this half's)
+template <int NBW, int G, int EX>
+struct ExactShape {
+  static constexpr int LBF = EX ? NBW : 0, NSF = EX ? G : 0;
+  static constexpr int LBC = EX == 2 ? NBW / 2 : LBF;
+  static constexpr int NSB = EX == 2 ? G / 2 : NSF;
+};
+
+template <int PREC, int NBW, bool MULTI, bool GATHER = false, int EX = 0>
 __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
+  using XS = ExactShape<NBW, Pre<PREC, NBW, MULTI>::G, EX>;
+  constexpr int LBF = XS::LBF, NSF = XS::NSF, LBC = XS::LBC, NSB = XS::NSB;
   RLMD_KERNARG_PREFETCH(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const RowDims& d = a.d;
@@ -939,12 +1001,12 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     FwdConst<NBW> ka, kc;
     actor_const<NBW>(ka, an, a.ao, d);
     Pre<PREC, NBW, MULTI> pa, pc;
-    pre_issue<PREC, NBW, MULTI>(pa, an.wc, H1p, H1p, H2p / 16);
+    pre_issue<PREC, NBW, MULTI, LBF, NSF>(pa, an.wc, H1p, H1p, H2p / 16);
     // the target critic's constants and fc2 stream: issued after the policy's
     // layer 2 (with this first round they queued behind the policy's and delayed it)
     auto issue_critic = [&] {
       critic_const<NBW>(kc, cn, a.co, d, nb0);
-      pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
+      pre_issue<PREC, NBW, MULTI, LBC, NSF>(pc, cn.wc, H1p, H1p, nbw, nb0);
     };
     if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 0, L.ldx, row0, B);
     const Noise2 nz = pre_nz ? noise_pre(smp, d, a.t_tag, row0) : Noise2{{0.f, 0.f}};
@@ -952,9 +1014,9 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     stage_commit(sr, s2, d.S, xs, L.ldx, row0, B);
     __syncthreads();
     RLMD_TSR(16 * job + 2);
-    mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
-                               d.A, smem, L, nullptr, nullptr, row0, B, nullptr, nullptr, nullptr, 0, 0, issue_critic,
-                               6);
+    mlp_rows<PREC, NBW, MULTI, 0, LBF, NSF>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3,
+                                            sac ? an.p + a.ao.w4 : nullptr, d.A, smem, L, nullptr, nullptr, row0, B,
+                                            nullptr, nullptr, nullptr, 0, 0, issue_critic, 6);
     RLMD_TSR(16 * job + 3);
     // load-free sampling on the production path (no injected noise): see sample_rows
     if (pre_nz && d.A <= 2)
@@ -967,8 +1029,8 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
                   pre_nz);
     __syncthreads();
     RLMD_TSR(16 * job + 4);
-    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                               nullptr, row0, B, nullptr, nullptr, nullptr, nb0, nbw, NoHook(), 22);
+    mlp_rows<PREC, NBW, MULTI, 1, LBC, NSF>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L,
+                                            nullptr, nullptr, row0, B, nullptr, nullptr, nullptr, nb0, nbw, NoHook(), 22);
     RLMD_TSR(16 * job + 5);
     float* qt = (nxt ? a.qtn[job] : a.qt[job]) + p * B;
     if ((int)threadIdx.x < R && row0 + (int)threadIdx.x < B) qt[row0 + threadIdx.x] = hout[threadIdx.x * kHeadsMax];
@@ -985,30 +1047,31 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     FwdConst<NBW> kc;
     critic_const<NBW>(kc, cn, a.co, d, nb0);
     Pre<PREC, NBW, MULTI> pc, pw;
-    pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
+    pre_issue<PREC, NBW, MULTI, LBC, NSF>(pc, cn.wc, H1p, H1p, nbw, nb0);
     if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 1, L.ldx, row0, B);
     // the basis pass's stream (the transposed copy): after the forward's layer 2
     auto issue_basis = [&] {
-      if (upd) pre_issue<PREC, NBW, MULTI>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0);
+      if (upd) pre_issue<PREC, NBW, MULTI, LBF, NSB>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0);
     };
     stage_commit(sr, a.xsa, d.X, xs, L.ldx, row0, B);
     __syncthreads();
     if (job == 2) RLMD_TSR(61);
     if (!upd) {
-      mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.c1[g],
-                                 a.c2[g], row0, B, a.cm1[g], a.cm2[g], nullptr, nb0, nbw);
+      mlp_rows<PREC, NBW, MULTI, 1, LBC, NSF>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L,
+                                              a.c1[g], a.c2[g], row0, B, a.cm1[g], a.cm2[g], nullptr, nb0, nbw);
     } else {
       using T = typename CT<PREC>::T;
       T* aU = reinterpret_cast<T*>(smem + L.aU);
       uint8_t* m1s = reinterpret_cast<uint8_t*>(smem + L.m1s);
       // h1 is the same in both halves: half 0 writes it
       const FwdExtra<PREC> ex{p == 0 ? static_cast<T*>(a.hp1[g]) : nullptr, static_cast<T*>(a.hp2[g]), m1s, aU};
-      mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                                 nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw, issue_basis);
+      mlp_rows<PREC, NBW, MULTI, 1, LBC, NSF>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L,
+                                              nullptr, nullptr, row0, B, nullptr, a.cm2[g], &ex, nb0, nbw, issue_basis);
       // the backward basis of these rows: U1 = [h1 > 0] * (([h2 > 0] w3) W2), so
       // that the critic update forms dh1 = dq * U1 once dq is known (update.hip);
       // a half's partial U1 over its fc2 columns
-      basis_pass<PREC, NBW, MULTI>(pw, aU, L.lda1, cn.wt, H1p, H2p, m1s, a.u1[g] + p * ustr, row0, B, ks0, ke);
+      basis_pass<PREC, NBW, MULTI, LBF, NSB>(pw, aU, L.lda1, cn.wt, H1p, H2p, m1s, a.u1[g] + p * ustr, row0, B, ks0,
+                                             ke);
       if (blockIdx.x == 0 && p == 0) {  // snapshots of what the update reads while stepping it
         for (int c = threadIdx.x; c < d.H2; c += NT) a.w3s[g][c] = cn.p[a.co.w3 + c];
         if (threadIdx.x == 0) a.bsnap[g] = cn.p[a.co.b3];
@@ -1027,7 +1090,7 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     FwdConst<NBW> ka;
     actor_const<NBW>(ka, an, a.ao, d);
     Pre<PREC, NBW, MULTI> pa;
-    pre_issue<PREC, NBW, MULTI>(pa, an.wc, H1p, H1p, H2p / 16);
+    pre_issue<PREC, NBW, MULTI, LBF, NSF>(pa, an.wc, H1p, H1p, H2p / 16);
     if constexpr (GATHER) sr = stage_issue_g(a.hg.rb, grow, 2, L.ldx, row0, B);
     const bool pre_nz = a.eps_cur == nullptr && a.a_mode == 0;
     const Noise2 nz = pre_nz ? noise_pre(a.smp, d, a.a_tag, row0) : Noise2{{0.f, 0.f}};
@@ -1043,8 +1106,9 @@ __global__ void __launch_bounds__(NT) fwd_rows_kernel(FwdRowsArgs a) {
     using T = typename CT<PREC>::T;
     const bool fa = a.hp1a != nullptr;
     const FwdExtra<PREC> ex{static_cast<T*>(a.hp1a), static_cast<T*>(a.hp2a), nullptr, nullptr};  // null: not written
-    mlp_rows<PREC, NBW, MULTI>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3, sac ? an.p + a.ao.w4 : nullptr,
-                               d.A, smem, L, fa ? nullptr : a.h1a, fa ? nullptr : a.h2a, row0, B, a.am1, a.am2, &ex);
+    mlp_rows<PREC, NBW, MULTI, 0, LBF, NSF>(an, a.ao, ka, pa, xs, L.ldx, d.S, na, an.p + a.ao.w3,
+                                            sac ? an.p + a.ao.w4 : nullptr, d.A, smem, L, fa ? nullptr : a.h1a,
+                                            fa ? nullptr : a.h2a, row0, B, a.am1, a.am2, &ex);
     RLMD_TSR(82);
     if ((pre_nz || a.a_mode == 1) && a.eps_cur == nullptr && d.A <= 2)
       sample_rows<true>(an.p, a.ao, d, a.smp, xs, L.ldx, hout, a.a_mode, a.a_tag, nullptr, 0.f, 0.f, 0, a.logp, a.save,
@@ -1106,8 +1170,10 @@ __device__ __forceinline__ void bwd_mask(BwdMask<NBW>& k, const uint8_t* m1, con
   }
 }
 
-template <int PREC, int NBW, bool MULTI>
+template <int PREC, int NBW, bool MULTI, int EX = 0>
 __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
+  using XS = ExactShape<NBW, Pre<PREC, NBW, MULTI>::G, EX>;
+  constexpr int LBF = XS::LBF, NSF = XS::NSF, LBC = XS::LBC, NSB = XS::NSB;
   RLMD_KERNARG_PREFETCH(a);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const RowDims& d = a.d;
@@ -1135,7 +1201,7 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     const int h = g - a.nq, nrb = (B + R - 1) / R;
     const RowNet& an = a.actor;
     Pre<PREC, NBW, MULTI> pw;
-    pre_issue<PREC, NBW, MULTI>(pw, an.wt, H2p, H2p, H1p / 16);
+    pre_issue<PREC, NBW, MULTI, LBF, NSF>(pw, an.wt, H2p, H2p, H1p / 16);
     BwdMask<NBW> k;
     bwd_mask<NBW>(k, a.am1, a.am2, nullptr, a.ao, row0, B);
     const ElemMap m = elem_map(H2p);
@@ -1151,12 +1217,12 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     }
     __syncthreads();
     f32x4 acc[NBW];
-    mfma_rows<PREC, NBW, MULTI>(pw, aU, L.lda1, an.wt, H2p, H2p, H1p / 16, acc);
+    mfma_rows<PREC, NBW, MULTI, LBF, NSF>(pw, aU, L.lda1, an.wt, H2p, H2p, H1p / 16, acc);
     float* u = a.ua + (int64_t)h * nrb * H1p * R;
-    const int wave = threadIdx.x >> 6;
+    const int wave = wave_id<(EX > 0)>();
 #pragma unroll
     for (int i = 0; i < NBW; ++i) {
-      if (wave + NW * i < H1p / 16) {
+      if (EX || wave + NW * i < H1p / 16) {
         const int col = acc_col(i);
         f32x4 v;
 #pragma unroll
@@ -1170,12 +1236,12 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
   const bool upd = a.dqda[0] != nullptr;
   const int nbw = H2p / 16 / P, nb0 = p * nbw;  // this half's fc2 output bands
   Pre<PREC, NBW, MULTI> pc, pw;
-  pre_issue<PREC, NBW, MULTI>(pc, cn.wc, H1p, H1p, nbw, nb0);
+  pre_issue<PREC, NBW, MULTI, LBC, NSF>(pc, cn.wc, H1p, H1p, nbw, nb0);
   FwdConst<NBW> kc;
   critic_const<NBW>(kc, cn, a.co, d, nb0);
   float w1a[NBW][NHF];  // W1[c][S + j] of this lane's accumulator columns (fused actor update)
   // the basis pass's stream: after the forward's layer 2 (as fwd_rows' critic jobs)
-  auto issue_basis = [&] { pre_issue<PREC, NBW, MULTI>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0); };
+  auto issue_basis = [&] { pre_issue<PREC, NBW, MULTI, LBF, NSB>(pw, cn.wt, H2p, ke, H1p / 16, 0, ks0); };
   if (upd) {
     const __amdgpu_buffer_rsrc_t rp = rlmd_rsrc(cn.p, a.co.size * 4);
 #pragma unroll
@@ -1189,8 +1255,8 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
   stage_rows(a.x, d.X, xs, L.ldx, row0, B);
   __syncthreads();
   if (!upd) {
-    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, a.e1[g],
-                               a.e2[g], row0, B, a.em1[g], a.em2[g], nullptr, nb0, nbw);
+    mlp_rows<PREC, NBW, MULTI, 1, LBC, NSF>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L,
+                                            a.e1[g], a.e2[g], row0, B, a.em1[g], a.em2[g], nullptr, nb0, nbw);
   } else {
     // the critic on (s, a_new) and its input gradient dq/da per row: the basis
     // pass [h1 > 0] * (([h2 > 0] w3) W2) contracted with W1[:, S:S+A] (the
@@ -1200,11 +1266,11 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
     const uint8_t* m1s = reinterpret_cast<const uint8_t*>(smem + L.m1s);
     float* part = reinterpret_cast<float*>(smem + L.part);
     const FwdExtra<PREC> ex{nullptr, nullptr, reinterpret_cast<uint8_t*>(smem + L.m1s), aU};
-    mlp_rows<PREC, NBW, MULTI, 1>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L, nullptr,
-                               nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw, issue_basis);
+    mlp_rows<PREC, NBW, MULTI, 1, LBC, NSF>(cn, a.co, kc, pc, xs, L.ldx, d.X, 1, cn.p + a.co.w3, nullptr, 1, smem, L,
+                                            nullptr, nullptr, row0, B, nullptr, nullptr, &ex, nb0, nbw, issue_basis);
     f32x4 acc[NBW];
-    mfma_rows<PREC, NBW, MULTI>(pw, aU, L.lda1, cn.wt, H2p, ke, H1p / 16, acc, 0, ks0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    mfma_rows<PREC, NBW, MULTI, LBF, NSB>(pw, aU, L.lda1, cn.wt, H2p, ke, H1p / 16, acc, 0, ks0);
+    const int lane = threadIdx.x & 63, wave = wave_id<(EX > 0)>();
     float pd[4][NHF];
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg)
@@ -1212,7 +1278,7 @@ __global__ void __launch_bounds__(NT) qeval_rows_kernel(QEvalArgs a) {
       for (int j = 0; j < NHF; ++j) pd[rg][j] = 0.f;
 #pragma unroll
     for (int i = 0; i < NBW; ++i) {
-      if (wave + NW * i < H1p / 16) {
+      if (EX || wave + NW * i < H1p / 16) {
         const int col = acc_col(i);
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
@@ -1693,8 +1759,31 @@ __global__ void __launch_bounds__(256) w2_copy_kernel(CopyJobs jobs, int H1, int
   }
 }
 
+// The exact-shape instantiations (fwd_rows_kernel's EX) exist for bf16, two bands
+// per wave, one K group: hidden widths 256 / 256.
 template <int PREC, int NBW, bool MULTI>
-void launch_kind(int kind, const void* args, dim3 grid, size_t lds, hipStream_t st) {
+constexpr bool kHasExact = PREC == RLMD_BF16 && NBW == 2 && !MULTI;
+
+// ex: rows_exact's choice for this launch (0: the run-time form)
+template <int PREC, int NBW, bool MULTI, int EX>
+void launch_exact(int kind, const void* args, dim3 grid, size_t lds, hipStream_t st) {
+  if (kind == 0)
+    hipLaunchKernelGGL((fwd_rows_kernel<PREC, NBW, MULTI, false, EX>), grid, dim3(NT), lds, st,
+                       *static_cast<const FwdRowsArgs*>(args));
+  else if (kind == 4)
+    hipLaunchKernelGGL((fwd_rows_kernel<PREC, NBW, MULTI, true, EX>), grid, dim3(NT), lds, st,
+                       *static_cast<const FwdRowsArgs*>(args));
+  else
+    hipLaunchKernelGGL((qeval_rows_kernel<PREC, NBW, MULTI, EX>), grid, dim3(NT), lds, st,
+                       *static_cast<const QEvalArgs*>(args));
+}
+
+template <int PREC, int NBW, bool MULTI>
+void launch_kind(int kind, const void* args, dim3 grid, size_t lds, hipStream_t st, int ex) {
+  if constexpr (kHasExact<PREC, NBW, MULTI>) {
+    if (ex == 1) return launch_exact<PREC, NBW, MULTI, 1>(kind, args, grid, lds, st);
+    if (ex == 2) return launch_exact<PREC, NBW, MULTI, 2>(kind, args, grid, lds, st);
+  }
   switch (kind) {
     case 0:
       hipLaunchKernelGGL((fwd_rows_kernel<PREC, NBW, MULTI>), grid, dim3(NT), lds, st,
@@ -1727,31 +1816,42 @@ void launch_kind(int kind, const void* args, dim3 grid, size_t lds, hipStream_t 
 // NBW = column blocks per wave (8 waves x 16 columns each), MULTI when the K
 // loop needs more than the 16 prefetched fragments per lane.
 template <int PREC>
-int launch_prec(const RowDims& d, int kind, const void* args, int ny, hipStream_t st, int extra_x, int nz) {
+int launch_prec(const RowDims& d, int kind, const void* args, int ny, hipStream_t st, int extra_x, int nz, int ex) {
   const int H = d.H1p > d.H2p ? d.H1p : d.H2p;
   const dim3 grid((d.B + R - 1) / R + extra_x, ny, nz);
   const size_t lds = (size_t)lds_layout(d).total;
   const int nsteps = H / CT<PREC>::KS;
   if (H <= 128) {
-    if (nsteps <= 16) launch_kind<PREC, 1, false>(kind, args, grid, lds, st);
-    else launch_kind<PREC, 1, true>(kind, args, grid, lds, st);
+    if (nsteps <= 16) launch_kind<PREC, 1, false>(kind, args, grid, lds, st, ex);
+    else launch_kind<PREC, 1, true>(kind, args, grid, lds, st, ex);
   } else if (H <= 256) {
-    if (nsteps <= 8) launch_kind<PREC, 2, false>(kind, args, grid, lds, st);
-    else launch_kind<PREC, 2, true>(kind, args, grid, lds, st);
+    if (nsteps <= 8) launch_kind<PREC, 2, false>(kind, args, grid, lds, st, ex);
+    else launch_kind<PREC, 2, true>(kind, args, grid, lds, st, ex);
   } else {
-    launch_kind<PREC, 4, true>(kind, args, grid, lds, st);
+    launch_kind<PREC, 4, true>(kind, args, grid, lds, st, ex);
   }
   RLMD_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_rows(const RowDims& d, int kind, const void* args, int ny, hipStream_t st, int extra_x = 0, int nz = 1) {
+int launch_rows(const RowDims& d, int kind, const void* args, int ny, hipStream_t st, int extra_x = 0, int nz = 1,
+                int ex = 0) {
   RLMD_CHECK(d.H1 <= 512 && d.H2 <= 512, "row kernels: hidden widths up to 512");
   RLMD_CHECK(d.A <= RLMD_MAX_ACTION, "row kernels: too many actions");
   RLMD_CHECK(lds_layout(d).total <= 160 * 1024, "row kernels: LDS budget exceeded");
   if (d.B <= 0) return 0;
-  return d.prec == RLMD_BF16 ? launch_prec<RLMD_BF16>(d, kind, args, ny, st, extra_x, nz)
-                             : launch_prec<RLMD_FP32>(d, kind, args, ny, st, extra_x, nz);
+  return d.prec == RLMD_BF16 ? launch_prec<RLMD_BF16>(d, kind, args, ny, st, extra_x, nz, ex)
+                             : launch_prec<RLMD_FP32>(d, kind, args, ny, st, extra_x, nz, ex);
+}
+
+// The exact-shape form of fwd_rows / qeval_rows for this launch: 0 (the run-time
+// form) unless the caller allows it and the shape is the one those instantiations
+// are compiled for — bf16, H1p = H2p = 256 (16 bands = NW * 2, 8 K-steps = one
+// group); then 1 unsplit, 2 under the column split.  Must agree with launch_prec's
+// choice of <bf16, 2, false> (kHasExact).
+int rows_exact(const RowDims& d, int split, bool allow) {
+  if (!allow || d.prec != RLMD_BF16 || d.H1p != 256 || d.H2p != 256) return 0;
+  return split == 2 ? 2 : 1;
 }
 
 }  // namespace
@@ -1769,7 +1869,9 @@ extern "C" int rlmd_debug_ts_rows(unsigned long long* out) {
 
 namespace rlmd {
 
-int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split) {
+int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split, bool exact, bool* took_exact) {
+  const int ex = rows_exact(a.d, split, exact);
+  if (took_exact) *took_exact = ex != 0;
   RLMD_CHECK(a.y0 == 0 || a.y0 == 2, "fwd_rows: y0 is 0 or 2");
   RLMD_CHECK(a.npair == 0 || (a.y0 == 0 && a.s2n && a.qtn[0] && a.qtn[1]), "fwd_rows: target pairing buffers");
   RLMD_CHECK(split == 1 || (split == 2 && a.u1[0] && a.d.H2p % 64 == 0),
@@ -1779,19 +1881,21 @@ int fwd_rows_launch(const FwdRowsArgs& a, hipStream_t st, int split) {
     RLMD_CHECK(a.d.prec == RLMD_BF16 && R * lds_layout(a.d).ldx <= NT && a.hg.rb.n_steps <= 1 && a.hg.nk >= 1 &&
                    (a.npair == 0 || a.hg.nk >= 2) && a.eps_next == nullptr && a.eps_cur == nullptr,
                "fwd_rows: staging by index takes bf16, single-step rows up to 32 wide");
-    return launch_rows(a.d, 4, &a, ny + fwd_rows_gather_y(a.d.B, a.hg.nk), st, 0, split);
+    return launch_rows(a.d, 4, &a, ny + fwd_rows_gather_y(a.d.B, a.hg.nk), st, 0, split, ex);
   }
-  return launch_rows(a.d, 0, &a, ny, st, 0, split);
+  return launch_rows(a.d, 0, &a, ny, st, 0, split, ex);
 }
 int fwd_rows_gather_y(int B, int nk) {
   const int nrb = (B + R - 1) / R, per = (B + kGatherRows - 1) / kGatherRows;
   return (nk * per + nrb - 1) / nrb;
 }
-int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split) {
+int qeval_rows_launch(const QEvalArgs& a, int nq, hipStream_t st, int split, bool exact, bool* took_exact) {
+  const int ex = rows_exact(a.d, split, exact);
+  if (took_exact) *took_exact = ex != 0;
   RLMD_CHECK(a.nq == nq && (a.nab == 0 || (a.ua && a.wheads && a.am1 && a.am2)), "qeval_rows: head jobs need their buffers");
   RLMD_CHECK(a.split == split && (split == 1 || (split == 2 && a.dqda[0] && a.d.H2p % 64 == 0)),
              "qeval_rows: a column split needs the fused actor path and H2p a multiple of 64");
-  return launch_rows(a.d, 1, &a, nq * split + a.nab, st);
+  return launch_rows(a.d, 1, &a, nq * split + a.nab, st, 0, 1, ex);
 }
 // cbwd: dh1 columns in halves when each half is a whole number of column blocks
 // per wave (the per-workgroup W2^T stream is the kernel's cost)
